@@ -11,8 +11,13 @@ GPUs ("strong" scaling: 65 536 on 1 GPU, 8 192 per GPU on 8); envs are
 independent, so each rank owns a contiguous global env range (seeds = global
 index) and no data-path collective runs.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--envs 65536]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--envs 65536] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the result line.  --full adds everything else
+the benchmark measures, each in runs of its own after the timed window: the same steps with several steps
+per graph launch, per-kernel HIP-event times and the roofline block, the episode mix and the CPU baseline.
+--dump-outputs DIR writes what the last timed step left in the caller's output tensors as DIR/<name>.npy.
 
 --gpus N decides the world size: without a launcher, N > 1 starts N rank processes of the same
 command (one per GPU, rendezvous on 127.0.0.1); under torchrun, WORLD_SIZE must equal N.
@@ -74,6 +79,14 @@ def parse():
     p.add_argument("--max-episode-steps", type=int, default=1000)
     p.add_argument("--obs-dtype", default=None, choices=["int64", "int32", "int16"])
     p.add_argument("--lanes-per-env", type=int, default=0, help="k_tick lanes per env (0 = engine default)")
+    p.add_argument("--full", action="store_true",
+                   help="also measure what the headline value does not need, after the timed window: the "
+                        "multi-step graph figure (--multi-steps), per-kernel times and the roofline block, the "
+                        "episode mix and the CPU baseline (--no-cpu-baseline skips that one)")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write the last timed step's outputs (observations of a fixed, "
+                        "seeded sample of envs; rewards, done, truncated, listed, was_reset of every env) as "
+                        "DIR/<name>.npy, float32 / float64, at most 64 MB in all")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-graph", action="store_true",
                    help="launch every step's kernels from the host instead of replaying the step as a hipGraph")
@@ -98,6 +111,8 @@ def parse():
                    help="(tests) the multi-rank control flow only: rank processes, gloo rendezvous, env ranges, the "
                         "barrier-bracketed timed loop on a no-op step and the slowest-rank time; no engine, no GPU")
     a = p.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
     a.launch = dict((kv.split("=")[0], int(kv.split("=")[1])) for kv in a.launch.split(",") if kv)
     for k, v in PRESETS[a.config].items():
         if getattr(a, k) is None:
@@ -217,6 +232,37 @@ def external_policy(eng, n_discrete=7):
         ids.add_(t).remainder_(n_discrete)
         torch.index_select(triples, 0, ids.view(-1), out=dst)
     return policy
+
+
+DUMP_OBS_BYTES = 48 << 20  # of --dump-outputs' 64 MB: the sampled observations as float32; the rest is per env
+
+
+def dump_outputs(path, src, suffix=""):
+    """--dump-outputs: the arrays a caller of the timed path holds after its last step, as
+    DIR/<name><suffix>.npy.  `src` is the Engine (its output tensors) or the StepGather (the node-wide
+    ones).  Observations (small integer codes, exact in float32) of a fixed, seeded sample of envs, the
+    sample's env indices beside them; rewards (float64) and the per-env flags of every env."""
+    import numpy as np
+    import torch
+
+    def get(name):
+        v = getattr(src, name)
+        return v() if callable(v) else v
+
+    obs = get("obs")
+    n = obs.shape[0]
+    k = max(1, min(n, DUMP_OBS_BYTES // (obs[0].numel() * 4)))
+    idx = np.sort(np.random.default_rng(0).choice(n, size=k, replace=False)) if k < n else np.arange(n)
+    arrays = {"obs_env_index": idx.astype(np.float64),
+              "obs": obs[torch.from_numpy(idx).to(obs.device)].to(torch.float32).cpu().numpy(),
+              "rewards": get("rewards").to(torch.float64).cpu().numpy()}
+    for name, attr in (("done", "done"), ("truncated", "truncated" if hasattr(src, "truncated") else "trunc"),
+                       ("listed", "listed"), ("was_reset", "was_reset")):
+        arrays[name] = get(attr).to(torch.float32).cpu().numpy()
+    assert sum(a.nbytes for a in arrays.values()) <= 64 * 10 ** 6, "--dump-outputs: more than 64 MB"
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + suffix + ".npy"), a)
 
 
 def env_range(rank, world, total_envs, envs_per_gpu=0):
@@ -434,12 +480,68 @@ def main():
             eng.gen_actions(step, 7)
             eng.step()
 
+    # without a graph the per-kernel events of --full are recorded in the timed launches themselves
     elapsed = timed_loop(one_step, args.steps // gsteps, args.warmup // gsteps, torch.cuda.synchronize, distributed,
-                         before_timing=None if use_graph else (lambda: eng.profile(True)))
+                         before_timing=(lambda: eng.profile(True)) if args.full and not use_graph else None)
+    if args.dump_outputs:
+        # the last timed step's outputs, before anything below steps the envs further: the node-wide
+        # tensors of the exchange on rank 0, else every rank's own
+        if gather:
+            if rank == 0:
+                dump_outputs(args.dump_outputs, gather)
+        else:
+            dump_outputs(args.dump_outputs, eng, "_rank%d" % rank if world > 1 else "")
+    if distributed:
+        elapsed = max_over_ranks(elapsed, torch.device("cuda", local))
+    value = total_envs * args.steps / elapsed
+    m = eng.builder.map
+    out = {
+        "metric": METRIC, "value": value, "unit": "env-steps/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": elapsed * 1e3 / args.steps, "higher_is_better": True,
+        "scaling": scaling, "vs_baseline": None, "dtype": "int32", "data": "synthetic", "full": args.full,
+        "config": {"workload": "%s: %d parallel %dx%d '%s' envs over %d GPU(s) (%d per GPU), %s, %d agents + "
+                               "%d zombies (minimum %d), MultiagentZombsoleEnv rewards, %s, 21x21x3 %s obs per "
+                               "agent written to HBM every step%s, TimeLimit %d, next-step autoreset, one step per "
+                               "graph launch%s" % (
+                                   args.config.upper(), total_envs, m.size[0], m.size[1], args.map, world, n_local,
+                                   args.rules, args.agents, args.zombies, args.min_zombies,
+                                   "a caller-side torch policy on the previous step's observations" if external
+                                   else "uniform Discrete(7) policy on device", args.obs_dtype,
+                                   " and all-gathered over RCCL with rewards/done/truncated" if gather else "",
+                                   args.max_episode_steps,
+                                   "" if gsteps == 1 else " (here %d: only every %d-th step's outputs visible)" % (
+                                       gsteps, gsteps)),
+                   "preset": args.config, "envs_per_gpu": n_local, "total_envs": total_envs, "map": args.map,
+                   "rules": args.rules, "agents": args.agents, "zombies": args.zombies,
+                   "minimum_zombies": args.min_zombies, "obs_dtype": args.obs_dtype,
+                   "parallelism": "env-sharded x%d (%s)" % (
+                       world, "RCCL all-gather of obs + rewards/done per step" if gather
+                       else "no data-path collective"), "launch": launch},
+        # --full only
+        "roofline": None, "cpu_baseline": None,
+    }
+    if args.full:
+        full_measurements(args, out, eng, one_step, lambda: step, builder, rank=rank, local=local, world=world,
+                          distributed=distributed, plain_graph=use_graph and not gather and not external and gsteps == 1)
+    if rank == 0:
+        os.write(json_fd, (json.dumps(out) + "\n").encode())
+    eng.close()
+    if distributed:
+        dist.destroy_process_group()
+
+
+def full_measurements(args, out, eng, one_step, steps_done, builder, rank, local, world, distributed, plain_graph):
+    """--full: what the benchmark measures beside its headline value, in runs of their own that continue the
+    timed window's trajectories (steps_done(): the steps one_step has run); the figures go into the result
+    line `out`."""
+    import torch
+    use_graph = not args.no_graph
+    launch = out["config"]["launch"]
+    n_local, total_envs = out["config"]["envs_per_gpu"], out["config"]["total_envs"]
     # the same workload with several steps per graph launch (the launch gap paid once per launch; the
     # outputs of a launch's earlier steps are overwritten): reported beside the headline, never as it
     multi = None
-    if use_graph and not gather and not external and gsteps == 1 and args.multi_steps > 1:
+    if plain_graph and args.multi_steps > 1:
         ms = max(d for d in range(1, args.multi_steps + 1) if args.steps % d == 0)
         if ms > 1:
             el = timed_loop(lambda: one_step(ms), args.steps // ms, max(1, -(-args.warmup // ms)),
@@ -449,6 +551,7 @@ def main():
             multi = {"graph_steps": ms, "value": total_envs * args.steps / el, "ms_per_step": el * 1e3 / args.steps,
                      "note": "%d steps per graph launch: only every %d-th step's outputs are visible to the caller; "
                              "not the headline" % (ms, ms)}
+    step = steps_done()
     prof_steps = args.steps
     if use_graph:
         # per-kernel HIP-event durations: the same steps launched one kernel at a time right after
@@ -474,9 +577,6 @@ def main():
         ends[1] += eng.trunc.sum()
     torch.cuda.synchronize()
     ends = ends.tolist()
-    if distributed:
-        elapsed = max_over_ranks(elapsed, torch.device("cuda", local))
-    value = total_envs * args.steps / elapsed
 
     # roofline of the dominant kernel (HIP-event durations on the engine's stream)
     m = eng.builder.map
@@ -528,54 +628,26 @@ def main():
                         issue[k] = {n: round(v, 4) for n, v in wl["kernels"][k].items() if n in keep}
         except Exception:
             issue = None
-    out = {
-        "metric": METRIC, "value": value, "unit": "env-steps/s", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": elapsed * 1e3 / args.steps, "higher_is_better": True,
-        "scaling": scaling, "vs_baseline": None, "dtype": "int32", "data": "synthetic",
-        "config": {"workload": "%s: %d parallel %dx%d '%s' envs over %d GPU(s) (%d per GPU), %s, %d agents + "
-                               "%d zombies (minimum %d), MultiagentZombsoleEnv rewards, %s, 21x21x3 %s obs per "
-                               "agent written to HBM every step%s, TimeLimit %d, next-step autoreset, one step per "
-                               "graph launch%s" % (
-                                   args.config.upper(), total_envs, m.size[0], m.size[1], args.map, world, n_local,
-                                   args.rules, args.agents, args.zombies, args.min_zombies,
-                                   "a caller-side torch policy on the previous step's observations" if external
-                                   else "uniform Discrete(7) policy on device", args.obs_dtype,
-                                   " and all-gathered over RCCL with rewards/done/truncated" if gather else "",
-                                   args.max_episode_steps,
-                                   "" if gsteps == 1 else " (here %d: only every %d-th step's outputs visible)" % (
-                                       gsteps, gsteps)),
-                   "preset": args.config, "envs_per_gpu": n_local, "total_envs": total_envs, "map": args.map,
-                   "rules": args.rules, "agents": args.agents, "zombies": args.zombies,
-                   "minimum_zombies": args.min_zombies, "obs_dtype": args.obs_dtype,
-                   "parallelism": "env-sharded x%d (%s)" % (
-                       world, "RCCL all-gather of obs + rewards/done per step" if gather
-                       else "no data-path collective"), "launch": launch,
-                   "episode_ends_per_step": {"done": ends[0] / mix_steps, "truncated": ends[1] / mix_steps,
-                                             # done or truncated: each is an autoreset at the next step
-                                             "fraction_of_envs": (ends[0] + ends[1]) / mix_steps / n_local,
-                                             "sample": "%d untimed steps after the timed window, rank 0" % mix_steps}},
-        "roofline": {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                     "frac": achieved / PEAK_HBM_GBS, "traffic": traffic,
-                     "algorithmic_bytes_per_step": dom_b * n_local,
-                     "kernel_ms_per_step": dom_ms, "launches_per_step": {
-                         "tick": prof["tick_n"] / prof_steps, "obs": prof["obs_n"] / prof_steps,
-                         "reset": prof["reset_n"] / prof_steps, "respawn": prof["respawn_n"] / prof_steps},
-                     "step_launch_ms": tick_ms, "k_obs_ms": obs_ms,
-                     "k_reset_ms": reset_ms, "k_respawn_ms": prof["respawn_ms"] / prof_steps,
-                     "step_launch_writes_obs": bool(fobs),
-                     "step_launch_resets": bool(fused),
-                     "issue": issue},
-        "cpu_baseline": None,
-    }
+    out["config"]["episode_ends_per_step"] = {
+        "done": ends[0] / mix_steps, "truncated": ends[1] / mix_steps,
+        # done or truncated: each is an autoreset at the next step
+        "fraction_of_envs": (ends[0] + ends[1]) / mix_steps / n_local,
+        "sample": "%d untimed steps after the timed window, rank 0" % mix_steps}
+    out["roofline"] = {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                       "frac": achieved / PEAK_HBM_GBS, "traffic": traffic,
+                       "algorithmic_bytes_per_step": dom_b * n_local,
+                       "kernel_ms_per_step": dom_ms, "launches_per_step": {
+                           "tick": prof["tick_n"] / prof_steps, "obs": prof["obs_n"] / prof_steps,
+                           "reset": prof["reset_n"] / prof_steps, "respawn": prof["respawn_n"] / prof_steps},
+                       "step_launch_ms": tick_ms, "k_obs_ms": obs_ms,
+                       "k_reset_ms": reset_ms, "k_respawn_ms": prof["respawn_ms"] / prof_steps,
+                       "step_launch_writes_obs": bool(fobs),
+                       "step_launch_resets": bool(fused),
+                       "issue": issue}
     if multi:
         out["multi_step_graph"] = multi
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args, builder)
-    if rank == 0:
-        os.write(json_fd, (json.dumps(out) + "\n").encode())
-    eng.close()
-    if distributed:
-        dist.destroy_process_group()
 
 
 if __name__ == "__main__":

@@ -15,7 +15,7 @@ for r in 1 2; do
       esac
       tag=$(echo "$v" | tr ',=' '_-')
       out=gpurun_out/abl_${cfg}_${tag}_$r.json
-      timeout -k 10 180 python bench.py $(args $cfg) --steps ${STEPS:-200} --warmup 20 --no-cpu-baseline $lflag > $out 2> $out.err || { tail -5 $out.err; exit 1; }
+      timeout -k 10 180 python bench.py $(args $cfg) --steps ${STEPS:-200} --warmup 20 --full --no-cpu-baseline $lflag > $out 2> $out.err || { tail -5 $out.err; exit 1; }
       python -c "import json;d=json.load(open('$out'));r=d['roofline'];print('$r $cfg $v', round(d['value']/1e6,2), 'M/s ms', round(d['ms_per_step'],4), 'step', round(r['step_launch_ms'],4), 'obs', round(r['k_obs_ms'],4), 'reset', round(r['k_reset_ms'],4), 'respawn', round(r['k_respawn_ms'],4))"
     done
   done

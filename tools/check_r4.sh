@@ -10,9 +10,10 @@ if [ -z "$NO_TESTS" ]; then
   tail -2 gpurun_out/pytest_gpu.log
 fi
 args() { case $1 in n8) echo "--config c3 --envs 8192";; c5n8) echo "--config c5 --envs 8192";; *) echo "--config $1";; esac; }
+OUT=${OUT:-bench_out}; mkdir -p "$OUT"
 for cfg in ${CFGS:-}; do
-  timeout -k 10 180 python bench.py $(args $cfg) --steps 200 --warmup 20 --no-cpu-baseline > gpurun_out/bench_$cfg.json 2> gpurun_out/bench_$cfg.err || { tail -5 gpurun_out/bench_$cfg.err; exit 1; }
-  python -c "import json;d=json.load(open('gpurun_out/bench_$cfg.json'));r=d['roofline'];print('$cfg', round(d['value']/1e6,1), 'M/s ms', round(d['ms_per_step'],4), 'step', round(r['step_launch_ms'],4), 'obs', round(r['k_obs_ms'],4), 'reset', round(r['k_reset_ms'],4), 'respawn', round(r['k_respawn_ms'],4))"
+  timeout -k 10 180 python bench.py $(args $cfg) --steps 200 --warmup 20 --full --no-cpu-baseline > "$OUT/bench_$cfg.json" 2> "$OUT/bench_$cfg.err" || { tail -5 "$OUT/bench_$cfg.err"; exit 1; }
+  python -c "import json;d=json.load(open('$OUT/bench_$cfg.json'));r=d['roofline'];print('$cfg', round(d['value']/1e6,1), 'M/s ms', round(d['ms_per_step'],4), 'step', round(r['step_launch_ms'],4), 'obs', round(r['k_obs_ms'],4), 'reset', round(r['k_reset_ms'],4), 'respawn', round(r['k_respawn_ms'],4))"
 done
 if [ -n "$AB_VARIANTS" ]; then
   CFGS="${AB_CFGS:-n8}" VARIANTS="$AB_VARIANTS" STEPS=${AB_STEPS:-200} bash tools/ab_launch.sh > gpurun_out/ab_launch.log 2>&1 || { tail -5 gpurun_out/ab_launch.log; exit 1; }

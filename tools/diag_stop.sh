@@ -10,7 +10,7 @@ for cfg in ${CFGS:-c3 c5 c4}; do
     lib=libzombsole_amd/_build/libzombsole_mi355x.so
     [ "$v" != product ] && lib=libzombsole_amd/_build/libzombsole_mi355x_$v.so
     timeout -k 10 120 python bench.py --config "$cfg" --engine-lib "$lib" --no-graph --steps 100 --warmup 10 \
-        --no-cpu-baseline > "$OUT/${cfg}_$v.json" 2> "$OUT/${cfg}_$v.err" || { echo "$cfg $v failed"; tail -5 "$OUT/${cfg}_$v.err"; exit 1; }
+        --full --no-cpu-baseline > "$OUT/${cfg}_$v.json" 2> "$OUT/${cfg}_$v.err" || { echo "$cfg $v failed"; tail -5 "$OUT/${cfg}_$v.err"; exit 1; }
     python -c "import json,sys;d=json.load(open(sys.argv[1]));r=d['roofline'];print(sys.argv[2], sys.argv[3], 'tick', round(r['step_launch_ms']*1e3,1), 'us  obs', round(r['k_obs_ms']*1e3,1), 'us  respawn', round(r['k_respawn_ms']*1e3,1))" "$OUT/${cfg}_$v.json" "$cfg" "$v"
   done
 done

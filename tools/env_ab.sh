@@ -13,7 +13,7 @@ for rep in 1 2; do
     for v in "${VL[@]}"; do
       name="${v%%:*}"; envs="${v#*:}"
       f="$OUT/${cname}_${name}_$rep"
-      env $envs timeout -k 10 180 python bench.py $cargs --steps ${STEPS:-300} --warmup 30 --no-cpu-baseline > "$f.json" 2> "$f.err" \
+      env $envs timeout -k 10 180 python bench.py $cargs --steps ${STEPS:-300} --warmup 30 --full --no-cpu-baseline > "$f.json" 2> "$f.err" \
           || { echo "variant $cname/$name failed"; tail -5 "$f.err"; exit 1; }
       python -c "import json,sys;d=json.load(open(sys.argv[1]));print('%-10s %-10s rep %s %8.2f M/s %.4f ms' % (sys.argv[2], sys.argv[3], sys.argv[4], d['value']/1e6, d['ms_per_step']))" "$f.json" "$cname" "$name" "$rep"
     done

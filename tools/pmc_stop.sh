@@ -13,7 +13,7 @@ for v in ${VARIANTS:-product stop1 stop2 stop3 stop5}; do
   [ "$v" != product ] && lib=libzombsole_amd/_build/libzombsole_mi355x_$v.so
   timeout -s KILL 120 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR \
       -T --output-format csv -d "$OUT/$v" -o run -- python3 bench.py --config "${CFG:-c5}" --engine-lib "$lib" --no-graph \
-      --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/$v.log" 2>&1 || { echo "pmc pass $v failed"; tail -5 "$OUT/$v.log"; exit 1; }
+      --steps 20 --warmup 5 --full --no-cpu-baseline > "$OUT/$v.log" 2>&1 || { echo "pmc pass $v failed"; tail -5 "$OUT/$v.log"; exit 1; }
 done
 python3 - "$OUT" ${VARIANTS:-product stop1 stop2 stop3 stop5} <<'PY' | tee "$OUT/summary.txt"
 import csv, glob, os, sys

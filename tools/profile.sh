@@ -7,7 +7,7 @@ cd /tmp && export TMPDIR=/tmp && cd - > /dev/null || exit 2
 ROOT=$PWD
 OUT=$ROOT/gpurun_out/prof
 mkdir -p "$OUT"
-BENCH="bench.py --steps ${STEPS:-50} --warmup 10 --no-cpu-baseline ${BENCH_ARGS}"
+BENCH="bench.py --steps ${STEPS:-50} --warmup 10 --full --no-cpu-baseline ${BENCH_ARGS}"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -T --output-format csv -d "$OUT/kt" -o run -- python3 $BENCH \
     > "$OUT/kt.log" 2>&1 || { echo "kernel-trace pass failed"; tail -5 "$OUT/kt.log"; exit 1; }
 echo "kernel-trace ok"

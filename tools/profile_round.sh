@@ -15,10 +15,10 @@ if [ -z "$NO_TESTS" ]; then
   tail -1 "$OUT/pytest_gpu.log"
 fi
 if [ -z "$NO_BENCH" ]; then
-  timeout -k 10 300 python bench.py > "$OUT/bench_default.log" 2>&1 || { tail -5 "$OUT/bench_default.log"; exit 1; }
+  timeout -k 10 300 python bench.py --full > "$OUT/bench_default.log" 2>&1 || { tail -5 "$OUT/bench_default.log"; exit 1; }
   tail -1 "$OUT/bench_default.log" | cut -c1-200
   for cfg in ${CFGS:-c3 c2 c4 c5 n8}; do
-      timeout -k 10 180 python bench.py $(args $cfg) --steps 200 --warmup 20 --no-cpu-baseline > "$OUT/bench_$cfg.log" 2>&1 \
+      timeout -k 10 180 python bench.py $(args $cfg) --steps 200 --warmup 20 --full --no-cpu-baseline > "$OUT/bench_$cfg.log" 2>&1 \
           || { tail -5 "$OUT/bench_$cfg.log"; exit 1; }
   done
 fi
@@ -26,14 +26,14 @@ cd /tmp && export TMPDIR=/tmp && cd - > /dev/null || exit 2
 for cfg in ${PCFGS:-c3 c4 c5 n8}; do
     P=$PWD/$OUT/prof_$cfg
     mkdir -p "$P"
-    B="bench.py $(args $cfg) --steps 50 --warmup 10 --no-cpu-baseline"
+    B="bench.py $(args $cfg) --steps 50 --warmup 10 --full --no-cpu-baseline"
     timeout -k 10 300 rocprofv3 --kernel-trace --stats -T --output-format csv -d "$P/kt" -o run -- python3 $B > "$P/kt.log" 2>&1 \
         || { echo "kernel-trace $cfg failed"; tail -5 "$P/kt.log"; exit 1; }
     for c in FETCH_SIZE WRITE_SIZE; do
         timeout -s KILL 300 rocprofv3 --pmc $c -T --output-format csv -d "$P/$c" -o run -- python3 $B > "$P/$c.log" 2>&1 \
             || { echo "pmc $c $cfg failed"; tail -5 "$P/$c.log"; exit 1; }
     done
-    bash tools/pmc_sq.sh "${TAG}_$cfg" $(args $cfg) --steps 20 --warmup 5 --no-cpu-baseline --no-graph > "$P/sq.log" 2>&1 \
+    bash tools/pmc_sq.sh "${TAG}_$cfg" $(args $cfg) --steps 20 --warmup 5 --full --no-cpu-baseline --no-graph > "$P/sq.log" 2>&1 \
         || { echo "pmc sq $cfg failed"; tail -5 "$P/sq.log"; exit 1; }
     echo "profiled $cfg"
 done

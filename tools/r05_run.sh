@@ -25,7 +25,7 @@ for b in "${BL[@]}"; do
   name="${b%%:*}"; a="${b#*:}"
   [ -z "$name" ] && continue
   f="$OUT/bench_$name"
-  timeout -k 10 180 python bench.py $a --steps ${STEPS:-200} --warmup 20 --no-cpu-baseline > "$f.json" 2> "$f.err" || { echo "bench $name failed"; tail -5 "$f.err"; exit 1; }
+  timeout -k 10 180 python bench.py $a --steps ${STEPS:-200} --warmup 20 --full --no-cpu-baseline > "$f.json" 2> "$f.err" || { echo "bench $name failed"; tail -5 "$f.err"; exit 1; }
   show "$f.json" "$name"
 done
 if [ -n "$FSTEP_TESTS" ]; then
@@ -37,13 +37,13 @@ if [ -n "$FSTEP_TESTS" ]; then
     name="${b%%:*}"; a="${b#*:}"
     [ -z "$name" ] && continue
     f="$OUT/bench_$name"
-    timeout -k 10 180 python bench.py $a --steps ${STEPS:-200} --warmup 20 --no-cpu-baseline > "$f.json" 2> "$f.err" || { echo "bench $name failed"; tail -5 "$f.err"; exit 1; }
+    timeout -k 10 180 python bench.py $a --steps ${STEPS:-200} --warmup 20 --full --no-cpu-baseline > "$f.json" 2> "$f.err" || { echo "bench $name failed"; tail -5 "$f.err"; exit 1; }
     show "$f.json" "$name"
   done
 fi
 if [ -n "$EXCHANGE" ]; then
   export MASTER_ADDR=127.0.0.1 MASTER_PORT=${PORT:-29533} RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 TORCHELASTIC_RUN_ID=$TAG
-  B="bench.py --config c5 --envs 8192 --gather --steps ${STEPS:-200} --warmup 20 --no-cpu-baseline"
+  B="bench.py --config c5 --envs 8192 --gather --steps ${STEPS:-200} --warmup 20 --full --no-cpu-baseline"
   timeout -k 10 180 python $B > "$OUT/bench_c5n8_gather.json" 2> "$OUT/bench_c5n8_gather.err" \
       || { tail -5 "$OUT/bench_c5n8_gather.err"; exit 1; }
   show "$OUT/bench_c5n8_gather.json" c5n8/gather-skipped
@@ -52,7 +52,7 @@ if [ -n "$EXCHANGE" ]; then
   show "$OUT/bench_c5n8_gather_self.json" c5n8/gather-self
   cd /tmp && export TMPDIR=/tmp && cd - > /dev/null || exit 2
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -T --output-format csv -d "$PWD/$OUT/prof_exchange" -o run -- \
-      python3 bench.py --config c5 --envs 8192 --gather --gather-self --steps 50 --warmup 10 --no-cpu-baseline \
+      python3 bench.py --config c5 --envs 8192 --gather --gather-self --steps 50 --warmup 10 --full --no-cpu-baseline \
       > "$OUT/prof_exchange.log" 2>&1 || { tail -5 "$OUT/prof_exchange.log"; exit 1; }
   echo "exchange traced"
 fi

@@ -32,6 +32,6 @@ for b in "${BL[@]}"; do
   name="${b%%:*}"; a="${b#*:}"
   [ -z "$name" ] && continue
   f="$OUT/bench_$name"
-  timeout -k 10 180 python bench.py $a --steps ${STEPS:-200} --warmup 20 --no-cpu-baseline > "$f.json" 2> "$f.err" || { echo "bench $name failed"; tail -5 "$f.err"; exit 1; }
+  timeout -k 10 180 python bench.py $a --steps ${STEPS:-200} --warmup 20 --full --no-cpu-baseline > "$f.json" 2> "$f.err" || { echo "bench $name failed"; tail -5 "$f.err"; exit 1; }
   show "$f.json" "$name"
 done

@@ -9,7 +9,7 @@ STEPS=${STEPS:-100}
 for v in "$@"; do
     IFS=';' read -r label envs args <<< "$v"
     log=gpurun_out/sweep/$label.log
-    env ZS_VERBOSE=1 $envs timeout -k 10 180 python bench.py --steps $STEPS --warmup 10 --no-cpu-baseline $args > "$log" 2>&1 || {
+    env ZS_VERBOSE=1 $envs timeout -k 10 180 python bench.py --steps $STEPS --warmup 10 --full --no-cpu-baseline $args > "$log" 2>&1 || {
         echo "$label FAILED"; tail -5 "$log"; exit 1; }
     python3 - "$log" "$label" <<'EOF'
 import json, sys
