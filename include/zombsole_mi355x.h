@@ -297,7 +297,10 @@ int zs_profile(zs_handle* h, int32_t enable);
 int zs_profile_read(zs_handle* h, double out[8]);
 /* Diagnostics: the launch configuration the handle chose (lanes per env, LDS images, which
  * observation kernel, fused / side-stream reset work, deferred respawn) as a one-line JSON
- * object, NUL-terminated and truncated to len bytes.  Returns ZS_OK. */
+ * object, NUL-terminated and truncated to len bytes.  "obs_kernel" names the kernel of a step's
+ * and an unmasked zs_reset's observations ("step launch": the step writes them itself),
+ * "obs_kernel_masked" that of a zs_reset / zs_observe with an env mask, "obs_encoders"
+ * ("patched", "select" or "") the encoders of k_obs_ring.  Returns ZS_OK. */
 int zs_describe(zs_handle* h, char* buf, int32_t len);
 /* Diagnostics: out[0], out[1] = the two pending-reset list counts, out[2] = the deferred-respawn
  * count (after everything queued on stream), out[3] = the list parity the next step drains. */

@@ -312,19 +312,7 @@ struct zs_handle {
     int G;          // lanes per env in k_tick
     int tick_waves = ZS_STEP_WAVES;  // k_tick's register budget (waves per SIMD it is compiled for)
     size_t lds;     // k_tick dynamic LDS bytes
-    ObsLayout obs_l;  // k_obs per-wave LDS image
-    int obs_wpg;      // k_obs waves (envs) per workgroup
-    int obs_pipe = 0;      // k_obs_pipe<NOBS> usable (NOBS = 1, 2, 4), else 0
-    int obs_ring = 0;      // k_obs_ring: encoder and writer waves through an LDS ring (zs_launch.obs_ring)
-    size_t obs_ring_bytes = 0;
-    int obs_bring = 0;     // k_obs_pbring: its unit slots (0: not used)
-    size_t obs_bring_bytes = 0;
-    int obs_patch = 0;     // k_obs_pipe's walk with the padded-table encoder and the staged flush (k_obs_patch)
-    size_t obs_patch_bytes = 0;
-    int obs_patch_wgs = 2;  // its workgroups (PATCH_WPG waves) per CU
-    int obs_gather = 0;    // else k_obs_gather<NOBS> usable (NOBS = 1, 2, 4), else 0 (k_obs)
-    int obs_gather_stat = 0;    // k_obs_gather reads the static words from LDS tables (zs_launch.obs_gather_stat)
-    ObsLayout obs_gl;      // its per-wave image
+    ObsPlan obs;    // the observation kernels of an unmasked and of a masked launch (zs_obs_plan.hpp)
     // zs_step_graph: one captured hipGraph per autoreset-list parity (the step alternates the two
     // pending-reset lists), replayed on the caller's stream; keyed by the caller's buffers
     // a few buffer sets cached (a caller alternating double-buffered outputs, vector.StepGather)
@@ -338,7 +326,6 @@ struct zs_handle {
     uint64_t gclock = 0;
     uint64_t* d_gstep = nullptr;  // [0] policy step counter (the step's policy reads it, the step's tail advances it)
     int graph_pol = 0;            // zs_step_graph is capturing a step with this policy (n_discrete), else 0
-    int obs_pipe_wgs = 8;  // k_obs_pipe workgroups per CU
     // next-step reset work on a side stream, concurrent with the tick (the two touch disjoint envs);
     // the caller's stream joins it before the observations
     int reset_side = 0;
@@ -533,73 +520,39 @@ static int choose_layout(zs_handle* h, int want_g, bool fused, int obs_bytes) {
     return fail(ZS_EINVAL, "entity table / map too large for the LDS image of one env");
 }
 
-extern "C" int zs_create(const zs_config* cfg, int device, zs_handle** out) {
-    if (!cfg || !out) return fail(ZS_EINVAL, "null argument");
-    int rc = validate(cfg);
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(device));
-    zs_handle* h = new zs_handle();
-    h->cfg = *cfg;
-    memset(&h->ov, 0, sizeof(h->ov));
-    if (cfg->launch) h->ov = *cfg->launch;
-    h->cfg.launch = nullptr;
-    h->device = device;
+// zs_create's handle until it succeeds: an early return frees it with everything allocated so far
+struct HandleOwner {
+    zs_handle* h;
+    ~HandleOwner() {
+        if (!h) return;
+        free_all(h);
+        delete h;
+    }
+};
+
+#define TRY(x)             \
+    do {                   \
+        int _r = (x);      \
+        if (_r) return _r; \
+    } while (0)
+
+// zs_create: the static tables of the map and the config, uploaded; *rank_order: the obstacles are in
+// row-major order
+static int create_static_tables(zs_handle* h, const zs_config* cfg, bool* rank_order) {
     const zs_map_desc& m = cfg->map;
     Dev& d = h->d;
-    memset(&d, 0, sizeof(d));
-    d.N = cfg->num_envs;
-    d.W = m.width;
-    d.H = m.height;
-    d.O = m.n_obstacles;
-    d.A = cfg->num_agents;
-    d.P = cfg->num_bots;
-    d.Z = std::max(cfg->initial_zombies, cfg->minimum_zombies);
-    d.E = d.A + d.P + d.Z;
-    d.OW = (d.O + 31) / 32;
-    d.DW = (d.W * d.H + 31) / 32;
-    d.nps = m.n_player_spawns;
-    d.nzs = m.n_zombie_spawns;
-    d.nobj = m.n_objectives;
-    d.ncand = std::max(d.nps ? d.nps : d.W * d.H, d.nzs ? d.nzs : d.W * d.H);
-    d.rules = cfg->rules;
-    d.reward_mode = cfg->reward_mode;
-    d.obs_scope = cfg->obs_scope;
-    d.obs_enc = cfg->obs_encoding;
-    d.obs_w = cfg->obs_width;
-    d.obs_dtype = cfg->obs_dtype;
-    d.max_steps = cfg->max_episode_steps;
-    d.initial_zombies = cfg->initial_zombies;
-    d.minimum_zombies = cfg->minimum_zombies;
-    d.flags = cfg->flags;
-    // zombie respawn as wave work after the tick (k_respawn) when its shuffle is long: the tick's
-    // leader would draw one word per candidate serially.  zs_launch.defer_respawn forces either.
-    {
-        const int cands = m.n_zombie_spawns ? m.n_zombie_spawns : d.W * d.H;
-        const int dr = h->ov.defer_respawn;
-        d.defer_respawn = d.minimum_zombies > 0 && (dr ? dr > 0 : cands > 64);
-    }
-
-    // the shuffle and execution of a tick's actions by the env's lanes (zs_tick.hpp grp_execute) instead of
-    // its leader lane alone; zs_launch.par_exec = -1 keeps the leader's serial loop (A/B, parity tests)
-    d.par_exec = h->ov.par_exec >= 0;
     // static tables
     std::vector<int16_t> cellmap((size_t)d.W * d.H, -1);
     std::vector<int32_t> oxy(d.O);
     std::vector<uint8_t> okind(d.O);
     for (int i = 0; i < d.O; i++) {
         int x = m.obstacle_xy[2 * i], y = m.obstacle_xy[2 * i + 1];
-        if (cellmap[(size_t)y * d.W + x] != -1) {
-            delete h;
-            return fail(ZS_EINVAL, "two obstacles on one cell");
-        }
+        if (cellmap[(size_t)y * d.W + x] != -1) return fail(ZS_EINVAL, "two obstacles on one cell");
         cellmap[(size_t)y * d.W + x] = (int16_t)i;
         oxy[i] = (int32_t)((uint32_t)x | ((uint32_t)y << 16));
         okind[i] = m.obstacle_kind[i];
     }
-    if (d.O > 32767) {
-        delete h;
-        return fail(ZS_EINVAL, "too many obstacles");
-    }
+    if (d.O > 32767) return fail(ZS_EINVAL, "too many obstacles");
     std::vector<uint32_t> obstbits(d.DW, 0);
     for (int i = 0; i < d.O; i++) {
         int cell = m.obstacle_xy[2 * i + 1] * d.W + m.obstacle_xy[2 * i];
@@ -607,11 +560,11 @@ extern "C" int zs_create(const zs_config* cfg, int device, zs_handle** out) {
     }
     // the observation store loop finds an obstacle's index as the rank of its cell among obstacle
     // cells (zs_obs.hpp), valid when the obstacles are in row-major order (every map-file parse)
-    bool rank_order = true;
+    *rank_order = true;
     for (int i = 1; i < d.O; i++)
         if (m.obstacle_xy[2 * i + 1] * d.W + m.obstacle_xy[2 * i] <=
             m.obstacle_xy[2 * i - 1] * d.W + m.obstacle_xy[2 * i - 2])
-            rank_order = false;
+            *rank_order = false;
     std::vector<uint32_t> boxbits(d.DW, 0);
     for (int i = 0; i < d.O; i++)
         if (m.obstacle_kind[i] == ZS_THING_BOX) {
@@ -641,15 +594,7 @@ extern "C" int zs_create(const zs_config* cfg, int device, zs_handle** out) {
     std::vector<int32_t> ac(cfg->agent_codes, cfg->agent_codes + d.A);
     std::vector<int32_t> bt(cfg->bot_types, cfg->bot_types + d.P);
 
-#define TRY(x)             \
-    do {                   \
-        int _r = (x);      \
-        if (_r) {          \
-            free_all(h);   \
-            delete h;      \
-            return _r;     \
-        }                  \
-    } while (0)
+
     int16_t* p_cellmap;
     uint32_t *p_objbits, *p_obstbits, *p_boxbits;
     int32_t *p_scell, *p_oprefix;
@@ -718,6 +663,12 @@ extern "C" int zs_create(const zs_config* cfg, int device, zs_handle** out) {
     d.agent_weapons = p_aw;
     d.agent_codes = p_ac;
     d.bot_types = p_bt;
+    return ZS_OK;
+}
+
+// zs_create: the per-env arrays, zeroed, and the handle's own buffers
+static int create_env_arrays(zs_handle* h, const zs_map_desc& m) {
+    Dev& d = h->d;
     const size_t N = d.N, E = d.E;
     TRY(dalloc(h, &d.pos, E * N));
     TRY(dalloc(h, &d.life, E * N));
@@ -733,7 +684,7 @@ extern "C" int zs_create(const zs_config* cfg, int device, zs_handle** out) {
     TRY(dalloc(h, &d.ovf, 1));
     {
         std::vector<int32_t> init(std::max(d.O, 1), 0);
-        for (int i = 0; i < d.O; i++) init[i] = okind[i] == ZS_THING_BOX ? 10 : 200;  // Box / Wall MAX_LIFE
+        for (int i = 0; i < d.O; i++) init[i] = m.obstacle_kind[i] == ZS_THING_BOX ? 10 : 200;  // Box / Wall MAX_LIFE
         int32_t* p_init;
         TRY(dupload(h, &p_init, init));
         d.hp_init = p_init;
@@ -780,124 +731,29 @@ extern "C" int zs_create(const zs_config* cfg, int device, zs_handle** out) {
         TRY(dalloc(h, &d.alog_n, N));
     }
     TRY(dalloc(h, &d.resp_count, 1));
-    {
-        // observation images: k_obs (four envs per workgroup when their images fit 64 KiB, else one;
-        // window map and staged HP while one image fits 32 KiB) and, when the step launch writes the
-        // observations itself (fobs), one env's image inside the tick / reset LDS (HP staged when the
-        // image still fits the MT twist buffer it aliases).  zs_launch.obs_win forces the per-cell
-        // entity scan (parity tests of that path).
-        const bool world = d.obs_scope == ZS_OBS_WORLD;
-        const int nobs = obs_count(d.obs_scope, d.reward_mode, d.A);
-        const int plane = world ? d.W * d.H : d.obs_w * d.obs_w;
-        const bool win = h->ov.obs_win >= 0;
-        ObsLayout L = obs_layout(nobs, plane, d.E, d.DW, d.OW, d.O, win, true);
-        if (L.bytes > 32 * 1024) L = obs_layout(nobs, plane, d.E, d.DW, d.OW, d.O, win, false);
-        if (L.bytes > 32 * 1024) L = obs_layout(nobs, plane, d.E, d.DW, d.OW, d.O, false, false);
-        if (L.bytes > 64 * 1024) {
-            free_all(h);
-            delete h;
-            return fail(ZS_EINVAL, "map too large for the observation kernel's LDS image");
-        }
-        // static tables (4 x DW words) beside the images: per k_obs workgroup, and inside the step
-        // launch's image region; zs_launch.obs_stat forces the per-cell static words (parity tests)
-        d.obs_stat = (rank_order && d.DW <= 1024 && h->ov.obs_stat >= 0) ? 4 * d.DW : 0;
-        h->obs_l = L;
-        h->obs_wpg = d.obs_stat * 4 + 4 * L.bytes <= 64 * 1024 ? 4 : 1;
-        // k_obs_pipe: surroundings of width 21, 1/2/4 observations, static tables, staged HP, window
-        // map, every entity on its own lane, prefetch arrays large enough (zs_launch.obs_pipe disables)
-        if (!world && d.obs_w == 21 && (nobs == 1 || nobs == 2 || nobs == 4) && d.obs_stat && L.hp_cap && L.win &&
-            d.O > 0 && d.E <= 64 && d.DW <= 64 * OBS_PF_D && d.O <= 64 * OBS_PF_H && d.OW <= 64 &&
-            d.obs_stat * 4 + 4 * L.bytes <= 64 * 1024 && h->ov.obs_pipe >= 0) {
-            h->obs_pipe = nobs;
-            // two workgroups (8 waves) per CU: measured at 65536 envs, 0.350 ms per launch against 0.375
-            // at 8 and 0.38 at 3-4 (a smaller set of env blocks in flight at once); one contiguous env
-            // range per wave instead of the strided walk measured slower (0.383)
-            h->obs_pipe_wgs = std::max(1, std::min(2, 160 * 1024 / (d.obs_stat * 4 + 4 * L.bytes)));
-            if (h->ov.obs_wgs > 0) h->obs_pipe_wgs = std::min(32, (int)h->ov.obs_wgs);
-        }
-        // The LDS-staged 16-B store kernels (k_obs_patch, k_obs_ring; zs_obs.hpp) for k_obs_pipe's shape,
-        // channels encoding.  They pay when every wave walks several envs (at 8192 envs, one env per wave,
-        // k_obs_pipe's per-cell stores measured 33 vs 36 us): int64 blocks from 48 envs per CU (C3 on one
-        // MI355X, k_obs_ring against k_obs_pipe: 12 288 envs 129.5 against 117.1 M env-steps/s, 16 384 123.7 /
-        // 121.4, 24 576 140.1 / 134.8, 32 768 153.6 / 147.1; 8 192 138.9 against 143.9, 10 240 (fused) 150.9 /
-        // 154.9; profiles/r05c_mid_sizes.log), narrower blocks at any count.  zs_launch.obs_lds = -1 keeps
-        // k_obs_pipe, 1 takes them at any count.
-        bool staged = false;
-        if (h->obs_pipe && d.obs_enc == ZS_ENC_CHANNELS && h->ov.obs_lds >= 0) {
-            const int ts = d.obs_dtype == ZS_DTYPE_I64 ? 8 : d.obs_dtype == ZS_DTYPE_I32 ? 4 : 2;
-            staged = ts < 8 || (long)d.N >= 48L * 256 || h->ov.obs_lds > 0;
-        }
-        // k_obs_patch: k_obs_pipe's walk with the padded-table encoder and the staged flush (maps up to
-        // 4095 x 4095, rows of the padded table in the workgroup's LDS).  zs_launch.obs_patch = -1 disables.
-        if (staged && d.OW <= 64 && (long)(d.W + 20) * 21 < 65536 && d.H < 4096) {
-            const int ts = d.obs_dtype == ZS_DTYPE_I64 ? 8 : d.obs_dtype == ZS_DTYPE_I32 ? 4 : 2;
-            const size_t pb = (size_t)patch_static_bytes(d.opad_n, d.O) +
-                              PATCH_WPG * (size_t)patch_wave_bytes(d.DW, d.O, obs_stage_slot_bytes(ts));
-            const int pz = h->ov.obs_patch;
-            const int nobs = obs_count(d.obs_scope, d.reward_mode, d.A);
-            if (pb <= 160 * 1024 && pz >= 0 &&
-                obs_attr(d.obs_dtype, OBSK_PATCH, nobs, 0, (int)pb) == hipSuccess) {
-                h->obs_patch = 1;
-                h->obs_patch_bytes = pb;
-                h->obs_patch_wgs = std::max(1, (int)(160 * 1024 / pb));
-                if (h->ov.obs_wgs > 0) h->obs_patch_wgs = std::min(32, (int)h->ov.obs_wgs);
-            }
-        }
-        // k_obs_ring (zs_obs.hpp): the staged flush with dedicated writer waves.  Measured on one MI355X
-        // (2 runs each): C3 (int64) observations 292 / 280 -> 285 / 273 us against its predecessor without
-        // writer waves; C5 (int16) even.  Default for int64 blocks; zs_launch.obs_ring forces either.
-        if (staged) {
-            const int ts = d.obs_dtype == ZS_DTYPE_I64 ? 8 : d.obs_dtype == ZS_DTYPE_I32 ? 4 : 2;
-            // the ring's encoders are k_obs_patch's when its tables fit (zs_launch.obs_ring_patch forces either)
-            const bool patched = h->obs_patch && h->ov.obs_ring_patch >= 0;
-            const size_t rb = patched ? (size_t)ring_lds_bytes(patch_static_bytes(d.opad_n, d.O), patch_enc_bytes(d.DW, d.O), ts, nobs)
-                                      : (size_t)ring_lds_bytes(16 * d.DW, L.bytes, ts, nobs);
-            const int rg = h->ov.obs_ring;
-            // default for int64 blocks, and for int16 ones with the padded-table encoders (C5 on one MI355X,
-            // 2 runs each: 215.2 / 216.5 us against k_obs_patch's 222.7 / 223.0)
-            if (rb <= 160 * 1024 && (rg ? rg > 0 : ts == 8 || (patched && ts == 2))) {
-                if (obs_attr(d.obs_dtype, OBSK_RING, nobs, patched ? 1 : 0, (int)rb) == hipSuccess) {
-                    h->obs_ring = patched ? 2 : 1;
-                    h->obs_ring_bytes = rb;
-                }
-            }
-        }
-        // k_obs_gather when the store-stream kernel does not apply (e.g. city128's 3689 obstacles):
-        // window-only static words and HP instead of per-env staging.  zs_launch.obs_gather disables.
-        if (!h->obs_pipe && !world && d.obs_w == 21 && (nobs == 1 || nobs == 2 || nobs == 4) &&
-            h->ov.obs_gather >= 0) {
-            ObsLayout G = obs_layout(nobs, plane, d.E, d.DW, d.OW, d.O, true, false);
-            if (4 * G.bytes <= 64 * 1024) {
-                h->obs_gather = nobs;
-                h->obs_gl = G;
-                // static words from the LDS tables (rank order, as obs_stat) instead of a global load
-                // round per window cell
-                const size_t gb = 4 * (size_t)G.bytes;
-                h->obs_gather_stat = d.obs_stat && gb + 16 * (size_t)d.DW <= 64 * 1024 && h->ov.obs_gather_stat >= 0;
-            }
-        }
-        // k_obs_pbring: k_obs_gather's window-only fetches as the encoders of a k_obs_ring-style ring, the
-        // things written over the windows (C4 on one MI355X: observations 180-184 us with k_obs_gather, 151 us
-        // with k_obs_pbring), when the dead-body and present rows fit the encoders' load rounds and two unit
-        // slots fit beside the static tables and the encoder regions.  zs_launch.obs_ring = -1 keeps k_obs_gather.
-        if (h->obs_gather && d.obs_stat && d.obs_enc == ZS_ENC_CHANNELS && d.E <= 64 && d.DW <= 64 * BRING_D &&
-            d.OW <= 64 * BRING_O && h->ov.obs_ring >= 0) {
-            const int ts = d.obs_dtype == ZS_DTYPE_I64 ? 8 : d.obs_dtype == ZS_DTYPE_I32 ? 4 : 2;
-            const int usp = pbring_slots(d.DW, d.OW, ts, nobs, 160 * 1024);
-            const size_t pbb = (size_t)pbring_fixed_bytes(d.DW, d.OW) + (size_t)usp * bring_unit_bytes(ts, nobs);
-            if (usp >= 2 && obs_attr(d.obs_dtype, OBSK_BRING, nobs, 1, (int)pbb) == hipSuccess) {
-                h->obs_bring = usp;
-                h->obs_bring_bytes = pbb;
-            }
-        }
-        // with the store-stream kernel available the observations are its job (measured faster than
-        // writing them from the tick workgroups at both 8192 and 65536 envs); zs_launch.fobs forces them
-        // into the step launch
-        d.obsl = L;
-        d.fobs = L.bytes + 4 * d.obs_stat <= 16 * 1024 && h->ov.fobs >= 0;
-        if (h->obs_pipe && h->ov.fobs <= 0) d.fobs = 0;
-        if (d.defer_respawn) d.fobs = 0;  // the observations must see k_respawn's zombies
-    }
+    return ZS_OK;
+}
+
+// zs_create: the observation kernels of the handle (zs_obs_plan.hpp), their LDS limits raised
+static int create_obs_plan(zs_handle* h, bool rank_order) {
+    Dev& d = h->d;
+    const ObsShape shape = {d.N, d.W, d.H, d.O, d.OW, d.DW, d.E, d.A, d.obs_scope, d.obs_enc, d.obs_w, d.obs_dtype,
+                            d.reward_mode, d.opad_n, rank_order, d.defer_respawn};
+    auto lds_ok = [](int kind, int nobs, int patched, int bytes, void* dtype) {
+        return obs_attr(*(const int*)dtype, kind, nobs, patched, bytes) == hipSuccess;
+    };
+    h->obs = obs_plan(shape, h->ov, lds_ok, &d.obs_dtype);
+    if (h->obs.error) return fail(ZS_EINVAL, h->obs.error);
+    d.obs_stat = h->obs.obs_stat;
+    d.obsl = h->obs.step_img;
+    d.fobs = h->obs.fobs;
+    return ZS_OK;
+}
+
+// zs_create: the step launch (fused or not, lanes per env, LDS copies), the reset launch's image and
+// the side stream of an unfused step's reset work
+static int create_step_layout(zs_handle* h) {
+    Dev& d = h->d;
     // Fused step launch (reset work + tick in one) when the whole launch is resident at once: then
     // the step is one latency-bound round and the reset work hides under the ticks (measured: 8192
     // envs, 1 round, fused 0.097 ms vs 0.13 ms).  With many rounds per CU (65536 envs) the reset
@@ -905,12 +761,12 @@ extern "C" int zs_create(const zs_config* cfg, int device, zs_handle** out) {
     // runs as its own short launch (0.54 ms vs 0.59 ms).  zs_launch.fused forces either.
     {
         const int obs_b = d.fobs ? d.obsl.bytes + 4 * d.obs_stat : 0;
-        TRY(choose_layout(h, cfg->lanes_per_env, true, obs_b));
+        TRY(choose_layout(h, h->cfg.lanes_per_env, true, obs_b));
         // 8 lanes per env when 16 would take the fused launch past one resident round and 8 take fewer rounds
         // (C3 on one MI355X: 16 384 envs, G = 16 two rounds 133.6 M env-steps/s, G = 8 one round 148.8 M;
         // 24 576 envs fused, G = 16 140.3 M, G = 8 143.5 M; 8 192 envs stay at G = 16, one round either way;
         // profiles/r05c_mid_sizes.log)
-        if (cfg->lanes_per_env <= 0 && h->G == 16 && d.E <= 16 && h->resident < h->want) {
+        if (h->cfg.lanes_per_env <= 0 && h->G == 16 && d.E <= 16 && h->resident < h->want) {
             const int r16 = (h->want + h->resident - 1) / h->resident;
             TRY(choose_layout(h, 8, true, obs_b));
             if ((h->want + h->resident - 1) / h->resident >= r16) TRY(choose_layout(h, 16, true, obs_b));
@@ -925,7 +781,7 @@ extern "C" int zs_create(const zs_config* cfg, int device, zs_handle** out) {
         // window that size costs no round trip, and the lanes' draws then reload it less often
         if (h->fused && h->ov.rw_need <= 0) d.rw_step = std::min(d.rw_cap, std::max(d.rw_step, 4 * h->G));
         if (!h->fused) {
-            TRY(choose_layout(h, cfg->lanes_per_env, false, obs_b));
+            TRY(choose_layout(h, h->cfg.lanes_per_env, false, obs_b));
             // k_tick's register budget: 5 waves per SIMD (96 VGPRs, 20 B of scratch per lane) unless 6 (80
             // VGPRs, 52 B of scratch on the leader's paths) saves a round of resident workgroups.  Measured
             // on one MI355X: C3 tick 95.6 -> 91.9 us and C4 185 -> 179 us at 5; C5 (16 384 workgroups:
@@ -948,37 +804,89 @@ extern "C" int zs_create(const zs_config* cfg, int device, zs_handle** out) {
             d.rlists_cap = d.nps + d.nzs;
         h->reset_lds = (size_t)reset_lds_bytes(d.E, d.DW, d.ncand, d.rlists_cap, obs_b);
     }
-    if (h->reset_lds > 160 * 1024) {
-        free_all(h);
-        delete h;
-        return fail(ZS_EINVAL, "map too large for the reset kernel's LDS image");
-    }
+    if (h->reset_lds > 160 * 1024) return fail(ZS_EINVAL, "map too large for the reset kernel's LDS image");
     // side-stream reset work (unfused steps; zs_launch.reset_stream keeps it on the caller's stream)
     if (!h->fused && h->ov.reset_stream >= 0) {
         h->reset_side = hipStreamCreateWithFlags(&h->s_reset, hipStreamNonBlocking) == hipSuccess &&
                         hipEventCreateWithFlags(&h->ev_rfork, hipEventDisableTiming) == hipSuccess &&
                         hipEventCreateWithFlags(&h->ev_rjoin, hipEventDisableTiming) == hipSuccess;
     }
-    if (h->reset_lds > 64 * 1024 && reset_lds_attr((int)h->reset_lds) != hipSuccess) {
-        free_all(h);
-        delete h;
+    if (h->reset_lds > 64 * 1024 && reset_lds_attr((int)h->reset_lds) != hipSuccess)
         return fail(ZS_EHIP, "cannot raise k_reset's dynamic LDS limit");
+    return ZS_OK;
+}
+
+extern "C" int zs_create(const zs_config* cfg, int device, zs_handle** out) {
+    if (!cfg || !out) return fail(ZS_EINVAL, "null argument");
+    *out = nullptr;
+    int rc = validate(cfg);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(device));
+    HandleOwner owner{new zs_handle()};
+    zs_handle* h = owner.h;
+    h->cfg = *cfg;
+    memset(&h->ov, 0, sizeof(h->ov));
+    if (cfg->launch) h->ov = *cfg->launch;
+    h->cfg.launch = nullptr;
+    h->device = device;
+    const zs_map_desc& m = cfg->map;
+    Dev& d = h->d;
+    memset(&d, 0, sizeof(d));
+    d.N = cfg->num_envs;
+    d.W = m.width;
+    d.H = m.height;
+    d.O = m.n_obstacles;
+    d.A = cfg->num_agents;
+    d.P = cfg->num_bots;
+    d.Z = std::max(cfg->initial_zombies, cfg->minimum_zombies);
+    d.E = d.A + d.P + d.Z;
+    d.OW = (d.O + 31) / 32;
+    d.DW = (d.W * d.H + 31) / 32;
+    d.nps = m.n_player_spawns;
+    d.nzs = m.n_zombie_spawns;
+    d.nobj = m.n_objectives;
+    d.ncand = std::max(d.nps ? d.nps : d.W * d.H, d.nzs ? d.nzs : d.W * d.H);
+    d.rules = cfg->rules;
+    d.reward_mode = cfg->reward_mode;
+    d.obs_scope = cfg->obs_scope;
+    d.obs_enc = cfg->obs_encoding;
+    d.obs_w = cfg->obs_width;
+    d.obs_dtype = cfg->obs_dtype;
+    d.max_steps = cfg->max_episode_steps;
+    d.initial_zombies = cfg->initial_zombies;
+    d.minimum_zombies = cfg->minimum_zombies;
+    d.flags = cfg->flags;
+    // zombie respawn as wave work after the tick (k_respawn) when its shuffle is long: the tick's
+    // leader would draw one word per candidate serially.  zs_launch.defer_respawn forces either.
+    {
+        const int cands = m.n_zombie_spawns ? m.n_zombie_spawns : d.W * d.H;
+        const int dr = h->ov.defer_respawn;
+        d.defer_respawn = d.minimum_zombies > 0 && (dr ? dr > 0 : cands > 64);
     }
-    if (getenv("ZS_VERBOSE"))
+
+    // the shuffle and execution of a tick's actions by the env's lanes (zs_tick.hpp grp_execute) instead of
+    // its leader lane alone; zs_launch.par_exec = -1 keeps the leader's serial loop (A/B, parity tests)
+    d.par_exec = h->ov.par_exec >= 0;
+    bool rank_order;
+    TRY(create_static_tables(h, cfg, &rank_order));
+    TRY(create_env_arrays(h, m));
+    TRY(create_obs_plan(h, rank_order));
+    TRY(create_step_layout(h));
+    const size_t N = d.N;
+    if (getenv("ZS_VERBOSE")) {
+        const ObsKernel &kf = h->obs.full, &km = h->obs.masked;
         fprintf(stderr, "zs_create: N=%d E=%d G=%d step_lds=%zu resident=%d reset_lds=%zu rw_cap=%d cand_cap=%d "
-                        "lists_cap=%d fused=%d fobs=%d obs_img=%d k_obs_img=%d x%d pipe=%d gather=%d pipe_wgs=%d reset_side=%d defer_respawn=%d\n",
+                        "lists_cap=%d fused=%d fobs=%d obs_img=%d obs=%s grid=%u block=%d lds=%d masked=%s block=%d lds=%d "
+                        "reset_side=%d defer_respawn=%d\n",
                 d.N, d.E, h->G, h->lds, h->resident, h->reset_lds, d.rw_cap, d.cand_cap, d.lists_cap, h->fused,
-                d.fobs, d.obsl.bytes, h->obs_l.bytes, h->obs_wpg, h->obs_pipe, h->obs_gather, h->obs_pipe_wgs,
-                h->reset_side, d.defer_respawn);
+                d.fobs, d.obsl.bytes, obs_kernel_name(kf.kind), obs_grid(kf, d.N), kf.block, kf.lds,
+                obs_kernel_name(km.kind), km.block, km.lds, h->reset_side, d.defer_respawn);
+    }
     if (d.O > 0) {
         size_t n = N * d.O;
         hipLaunchKernelGGL(k_init_obstacles, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, d);
         hipError_t le = hipGetLastError();
-        if (le != hipSuccess) {
-            free_all(h);
-            delete h;
-            return fail(ZS_EHIP, std::string("k_init_obstacles: ") + hipGetErrorString(le));
-        }
+        if (le != hipSuccess) return fail(ZS_EHIP, std::string("k_init_obstacles: ") + hipGetErrorString(le));
     }
     // every env starts "pending reset": the first zs_step (or zs_reset) builds its world
     hipLaunchKernelGGL(k_init_pending, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, 0, d, h->d_rlist[0],
@@ -986,22 +894,14 @@ extern "C" int zs_create(const zs_config* cfg, int device, zs_handle** out) {
     // default seeds: env index (every env has a valid stream even if never seeded)
     std::vector<uint64_t> seeds(N);
     for (size_t i = 0; i < N; i++) seeds[i] = i;
-    *out = h;
-    rc = zs_seed(h, 0, (int)N, seeds.data(), nullptr);
-    if (rc) {
-        zs_destroy(h);
-        *out = nullptr;
-        return rc;
-    }
+    TRY(zs_seed(h, 0, (int)N, seeds.data(), nullptr));
     hipError_t se = hipDeviceSynchronize();
-    if (se != hipSuccess) {
-        zs_destroy(h);
-        *out = nullptr;
-        return fail(ZS_EHIP, std::string("zs_create sync: ") + hipGetErrorString(se));
-    }
+    if (se != hipSuccess) return fail(ZS_EHIP, std::string("zs_create sync: ") + hipGetErrorString(se));
+    *out = h;
+    owner.h = nullptr;
     return ZS_OK;
-#undef TRY
 }
+#undef TRY
 
 extern "C" int zs_obs_shape(const zs_handle* h, int32_t out[4]) {
     if (!h || !out) return fail(ZS_EINVAL, "null argument");
@@ -1034,56 +934,12 @@ static int launch_obs(zs_handle* h, void* obs, const uint8_t* mask, hipStream_t 
     if (h->prof) HIPCHK(hipEventRecord(prof_event(h, &i0), s));
     if (env1 < 0) env1 = d.N;
     ObsLaunch o;
-    memset(&o, 0, sizeof(o));
+    o.k = mask ? h->obs.masked : h->obs.full;
+    o.grid = obs_grid(o.k, env1 - env0);
     o.obs = obs;
     o.mask = mask;
     o.env0 = env0;
     o.env1 = env1;
-    o.nobs = h->obs_pipe;
-    o.L = h->obs_l;
-    if (!mask && h->obs_ring) {  // encoder / writer waves, one workgroup per CU
-        const int ts = d.obs_dtype == ZS_DTYPE_I64 ? 8 : d.obs_dtype == ZS_DTYPE_I32 ? 4 : 2;
-        const int pair = ring_pair(ts, h->obs_pipe);
-        o.kind = OBSK_RING;
-        o.patched = h->obs_ring == 2;
-        o.grid = (unsigned)std::min((env1 - env0 + pair - 1) / pair, 256);
-        o.block = 64 * (RING_ENC + RING_WRT);
-        o.lds = h->obs_ring_bytes;
-    } else if (!mask && h->obs_patch) {  // every env of [env0, env1): the padded-table encoder's store stream
-        o.kind = OBSK_PATCH;
-        o.grid = (unsigned)std::min((env1 - env0 + PATCH_WPG - 1) / PATCH_WPG, 256 * h->obs_patch_wgs);
-        o.block = 64 * PATCH_WPG;
-        o.lds = h->obs_patch_bytes;
-    } else if (!mask && h->obs_pipe) {  // every env of [env0, env1), registered shape: the prefetching store stream
-        o.kind = OBSK_PIPE;
-        o.grid = (unsigned)std::min((env1 - env0 + 3) / 4, 256 * h->obs_pipe_wgs);
-        o.block = 256;
-        o.lds = (size_t)d.obs_stat * 4 + 4 * (size_t)h->obs_l.bytes;
-    } else if (!mask && h->obs_bring) {  // every env of [env0, env1): window-only encoders, writer waves
-        const int ts = d.obs_dtype == ZS_DTYPE_I64 ? 8 : d.obs_dtype == ZS_DTYPE_I32 ? 4 : 2;
-        const int pair = ring_pair(ts, h->obs_gather);
-        o.kind = OBSK_BRING;
-        o.nobs = h->obs_gather;
-        o.grid = (unsigned)std::min((env1 - env0 + pair - 1) / pair, 256);
-        o.block = 64 * (BRING_ENC + BRING_WRT);
-        o.lds = h->obs_bring_bytes;
-        o.L = h->obs_gl;
-        o.us = h->obs_bring;
-    } else if (h->obs_gather) {  // one env per wave, four per workgroup, window-only fetches
-        o.kind = OBSK_GATHER;
-        o.nobs = h->obs_gather;
-        o.grid = (unsigned)((d.N + 3) / 4);
-        o.block = 256;
-        o.lds = 4 * (size_t)h->obs_gl.bytes + (h->obs_gather_stat ? 16 * (size_t)d.DW : 0);
-        o.L = h->obs_gl;
-        o.stat = h->obs_gather_stat;
-    } else {
-        o.kind = OBSK_OBS;
-        o.grid = (unsigned)((d.N + h->obs_wpg - 1) / h->obs_wpg);
-        o.block = 64 * h->obs_wpg;
-        o.lds = (size_t)d.obs_stat * 4 + (size_t)h->obs_wpg * h->obs_l.bytes;
-        o.stat = d.obs_stat;
-    }
     HIPCHK(obs_launch(d.obs_dtype, o, s, d));
     if (h->prof) {
         HIPCHK(hipEventRecord(prof_event(h, &i1), s));
@@ -1559,17 +1415,16 @@ extern "C" int zs_profile_read(zs_handle* h, double* out) {
 extern "C" int zs_describe(zs_handle* h, char* buf, int32_t len) {
     if (!h || !buf || len <= 0) return fail(ZS_EINVAL, "null argument");
     const Dev& d = h->d;
-    const char* obs_kernel = d.fobs ? "step launch"
-                             : h->obs_pipe ? (h->obs_ring ? "k_obs_ring" : h->obs_patch ? "k_obs_patch" : "k_obs_pipe")
-                             : h->obs_bring ? "k_obs_pbring" : h->obs_gather ? "k_obs_gather" : "k_obs";
+    const ObsKernel& kf = h->obs.full;
     snprintf(buf, (size_t)len,
              "{\"envs\": %d, \"entities\": %d, \"lanes_per_env\": %d, \"step_kernel\": \"%s\", \"step_lds\": %zu, "
              "\"step_wgs_per_cu\": %d, \"rng_window\": %d, \"obs_kernel\": \"%s\", \"reset_side_stream\": %d, "
-             "\"reset_lds\": %zu, \"respawn\": \"%s\", \"tick_waves\": %d, \"rng_step\": %d, \"par_exec\": %d}",
-             d.N, d.E, h->G, h->fused ? "k_step" : "k_tick", h->lds, h->resident, d.rw_cap, obs_kernel,
-             h->reset_side,
+             "\"reset_lds\": %zu, \"respawn\": \"%s\", \"tick_waves\": %d, \"rng_step\": %d, \"par_exec\": %d, "
+             "\"obs_kernel_masked\": \"%s\", \"obs_encoders\": \"%s\"}",
+             d.N, d.E, h->G, h->fused ? "k_step" : "k_tick", h->lds, h->resident, d.rw_cap,
+             d.fobs ? "step launch" : obs_kernel_name(kf.kind), h->reset_side,
              h->reset_lds, d.defer_respawn ? "k_respawn" : "tick", h->fused ? ZS_FUSED_WAVES : h->tick_waves, d.rw_step,
-             d.par_exec);
+             d.par_exec, obs_kernel_name(h->obs.masked.kind), obs_encoders_name(kf));
     return ZS_OK;
 }
 
@@ -1628,8 +1483,7 @@ extern "C" int zs_death_log(zs_handle* h, int32_t env, int32_t* out_host, int32_
 static int obs_bytes_per_env(const zs_handle* h) {
     int32_t shp[4];
     zs_obs_shape(h, shp);
-    const int ts = h->d.obs_dtype == ZS_DTYPE_I64 ? 8 : h->d.obs_dtype == ZS_DTYPE_I32 ? 4 : 2;
-    return shp[0] * shp[1] * shp[2] * shp[3] * ts;
+    return shp[0] * shp[1] * shp[2] * shp[3] * obs_tsize(h->d.obs_dtype);
 }
 
 static HostLayout host_layout(const zs_handle* h) {

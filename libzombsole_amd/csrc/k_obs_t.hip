@@ -19,26 +19,28 @@ typedef int16_t TT;
 
 template <int NB>
 static void launch_nb(const ObsLaunch& o, hipStream_t s, const Dev& d) {
+    const ObsKernel& k = o.k;
     TT* out = (TT*)o.obs;
-    const dim3 g(o.grid), b(o.block);
-    switch (o.kind) {
+    const dim3 g(o.grid), b(k.block);
+    switch (k.kind) {
     case OBSK_RING:
-        if (o.patched) hipLaunchKernelGGL((k_obs_ring<TT, NB, true>), g, b, o.lds, s, d, out, o.L, o.env0, o.env1);
-        else hipLaunchKernelGGL((k_obs_ring<TT, NB, false>), g, b, o.lds, s, d, out, o.L, o.env0, o.env1);
+        if (k.patched) hipLaunchKernelGGL((k_obs_ring<TT, NB, true>), g, b, k.lds, s, d, out, k.L, o.env0, o.env1);
+        else hipLaunchKernelGGL((k_obs_ring<TT, NB, false>), g, b, k.lds, s, d, out, k.L, o.env0, o.env1);
         break;
-    case OBSK_BRING: hipLaunchKernelGGL((k_obs_pbring<TT, NB>), g, b, o.lds, s, d, out, o.env0, o.env1, o.us); break;
-    case OBSK_PATCH: hipLaunchKernelGGL((k_obs_patch<TT, NB>), g, b, o.lds, s, d, out, o.env0, o.env1); break;
-    case OBSK_PIPE: hipLaunchKernelGGL((k_obs_pipe<TT, NB>), g, b, o.lds, s, d, out, o.L, o.env0, o.env1); break;
-    default: hipLaunchKernelGGL((k_obs_gather<TT, NB>), g, b, o.lds, s, d, out, o.mask, o.L, o.stat); break;
+    case OBSK_BRING: hipLaunchKernelGGL((k_obs_pbring<TT, NB>), g, b, k.lds, s, d, out, o.env0, o.env1, k.us); break;
+    case OBSK_PATCH: hipLaunchKernelGGL((k_obs_patch<TT, NB>), g, b, k.lds, s, d, out, o.env0, o.env1); break;
+    case OBSK_PIPE: hipLaunchKernelGGL((k_obs_pipe<TT, NB>), g, b, k.lds, s, d, out, k.L, o.env0, o.env1); break;
+    default: hipLaunchKernelGGL((k_obs_gather<TT, NB>), g, b, k.lds, s, d, out, o.mask, k.L, k.stat); break;
     }
 }
 
 hipError_t ZS_OBS_FN(launch_obs)(const ObsLaunch& o, hipStream_t s, const Dev& d) {
-    if (o.kind == OBSK_OBS)
-        hipLaunchKernelGGL(k_obs<TT>, dim3(o.grid), dim3(o.block), o.lds, s, d, (TT*)o.obs, o.mask, o.L, o.stat);
-    else if (o.nobs == 1) launch_nb<1>(o, s, d);
-    else if (o.nobs == 2) launch_nb<2>(o, s, d);
-    else if (o.nobs == 4) launch_nb<4>(o, s, d);
+    const ObsKernel& k = o.k;
+    if (k.kind == OBSK_OBS)
+        hipLaunchKernelGGL(k_obs<TT>, dim3(o.grid), dim3(k.block), k.lds, s, d, (TT*)o.obs, o.mask, k.L, k.stat);
+    else if (k.nobs == 1) launch_nb<1>(o, s, d);
+    else if (k.nobs == 2) launch_nb<2>(o, s, d);
+    else if (k.nobs == 4) launch_nb<4>(o, s, d);
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }

@@ -19,6 +19,7 @@
 #include <stdint.h>
 
 #include "../../include/zombsole_mi355x.h"
+#include "zs_obs_plan.hpp"  // ObsLayout
 
 // minimum waves per SIMD the one-wave step / tick / reset kernels are compiled for (register budget):
 // 6 caps k_tick at 80 VGPRs (88 unbounded: 5 waves) for a few dwords of scratch on cold paths;
@@ -58,38 +59,6 @@ enum {
     S_ODIRTY,       // some obstacle may need removal at the next cleanup
     S_NSCAL
 };
-
-// one env's observation image in LDS (zs_obs.hpp)
-struct ObsLayout {
-    int win;     // window-map bytes (0: no window map, entities found by a per-cell scan)
-    int off_pos, off_life, off_cw, off_dead, off_opres, off_hp;
-    int hp_cap;  // obstacle HP staged in LDS (else read from HBM)
-    int bytes;   // one env's image
-};
-
-__host__ __device__ inline ObsLayout obs_layout(int nobs, int plane, int E, int DW, int OW, int O, bool winmap,
-                                                bool stage_hp) {
-    ObsLayout L;
-    int o = 0;
-    L.win = winmap ? ((nobs * plane + 15) / 16) * 16 : 0;
-    o += L.win;
-    L.off_pos = o;
-    o += E * 4;
-    o = ((o + 7) / 8) * 8;  // the store-stream kernels read {code word, life} pairs from off_life as 8 B
-    L.off_life = o;
-    o += E * 4;
-    L.off_cw = o;
-    o += E * 4;
-    L.off_dead = o;
-    o += DW * 4;
-    L.off_opres = o;
-    o += OW * 4;
-    L.off_hp = o;
-    L.hp_cap = stage_hp ? O : 0;
-    o += L.hp_cap * 4;
-    L.bytes = ((o + 15) / 16) * 16;
-    return L;
-}
 
 struct Dev {
     int N, W, H, O, A, P, Z, E, OW, DW, ncand, nps, nzs, nobj;

@@ -5,8 +5,8 @@
 //   k_obs_t.hip   once per observation dtype (-DZS_OBS_T=0/1/2): every observation kernel
 //   k_reset.hip   k_reset, k_respawn, k_list_filter
 //   engine.hip    the C ABI, the layout choice and the small helper kernels
-// Each unit exports plain host functions that launch its kernels; nothing but Dev, ObsLayout and
-// plain pointers crosses the units.
+// Each unit exports plain host functions that launch its kernels; nothing but Dev, the observation
+// plan's ObsKernel (zs_obs_plan.hpp) and plain pointers crosses the units.
 #pragma once
 #include "zs_device.hpp"
 
@@ -42,20 +42,13 @@ ZS_TICK_DECL(64)
 #undef ZS_TICK_DECL
 
 // observation kernels
-enum { OBSK_OBS = 0, OBSK_GATHER, OBSK_PIPE, OBSK_PATCH, OBSK_RING, OBSK_BRING };
+// one launch: the plan's kernel (zs_obs_plan.hpp) over the caller's buffers and env range
 struct ObsLaunch {
-    int kind;         // OBSK_*
-    int nobs;         // 1, 2 or 4 (k_obs: any)
-    int patched;      // k_obs_ring: padded-table encoders
+    ObsKernel k;
     unsigned grid;
-    unsigned block;
-    size_t lds;
     void* obs;
     const uint8_t* mask;
-    ObsLayout L;
     int env0, env1;
-    int stat;         // k_obs: static words staged; k_obs_gather: static words from LDS tables
-    int us;           // k_obs_pbring: unit slots of the ring
 };
 #define ZS_OBS_DECL(T)                                                              \
     hipError_t launch_obs_##T(const ObsLaunch& o, hipStream_t s, const Dev& d); \

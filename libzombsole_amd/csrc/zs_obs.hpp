@@ -19,6 +19,7 @@
 // obstacle (Box / Wall with its HP); dead body; objective; empty.
 #pragma once
 #include "zs_device.hpp"
+#include "zs_obs_plan.hpp"
 
 // static per-cell word: bits 0..15 obstacle index + 1 (0 = none), 16..18 obstacle code, bit 20 objective
 #define SC_OBST_MASK 0xffffu
@@ -29,11 +30,6 @@ typedef unsigned int zs_v4u __attribute__((ext_vector_type(4)));
 typedef unsigned int zs_v2u __attribute__((ext_vector_type(2)));
 typedef int zs_v2i __attribute__((ext_vector_type(2)));
 typedef int zs_v4i __attribute__((ext_vector_type(4)));
-
-// observations per env
-__host__ __device__ inline int obs_count(int scope, int reward_mode, int A) {
-    return scope == ZS_OBS_WORLD ? 1 : (reward_mode == ZS_REWARD_MULTI ? A : 1);
-}
 
 // workgroup b of nb -> XCD-contiguous virtual workgroup id (a bijection on [0, nb)).  The hardware
 // deals workgroups round-robin to the 8 XCDs; this gives each XCD a contiguous range of envs, so
@@ -507,8 +503,6 @@ __global__ void __launch_bounds__(256) k_obs(Dev d, T* out, const uint8_t* mask,
 #ifndef ZS_OBS_PIPE_WAVES
 #define ZS_OBS_PIPE_WAVES 4  // register budget: waves per SIMD the compiler must allow
 #endif
-#define OBS_PF_D 2   // prefetched dead-body words per lane   (DW <= 128: maps up to 4096 cells)
-#define OBS_PF_H 8   // prefetched obstacle HP words per lane (O <= 512)
 
 struct ObsPrefetch {
     int32_t pos, life, wp, pr;        // lane s < E: entity slot s
@@ -665,11 +659,7 @@ __global__ void __launch_bounds__(256, ZS_OBS_PIPE_WAVES) k_obs_pipe(Dev d, T* o
 template <typename T> struct obs_stage { typedef T type; };
 template <> struct obs_stage<int64_t> { typedef int32_t type; };
 
-// staging bytes: nblk consecutive channels blocks (one agent's, or every agent's of an env), shifted
-// by the destination's 16-B phase in elements
-__host__ __device__ constexpr int obs_stage_slot_bytes(int tsize, int nblk = 1) {
-    return (((nblk * 3 * 441 + 16 / tsize) * (tsize == 8 ? 4 : tsize) + 15) / 16) * 16;
-}
+// (the slot's size: obs_stage_slot_bytes, zs_obs_plan.hpp)
 
 // Stream one staged block to o: slot element k + mis / sizeof(T) holds output element k, so the
 // 16-B chunk q of the destination (counted from the 16-B boundary at or below o) reads the aligned
@@ -899,19 +889,7 @@ __global__ void __launch_bounds__(256) k_obs_gather(Dev d, T* out, const uint8_t
 // padded table entry (engine.hip: opad): bits 0..2 the code, bit 3 objective under a map obstacle,
 // bits 8..15 the life; opk (per obstacle): x | y << 12 | box << 24 | objective-under << 25
 #define OPAD_OBJ 8u
-__host__ __device__ constexpr int patch_list_bytes(int O) { return ((O * 8 + 15) / 16) * 16; }
-// static LDS of a workgroup: the padded table and the obstacles' packed cells
-__host__ __device__ constexpr int patch_static_bytes(int opad_n, int O) {
-    return ((opad_n * 2 + 15) / 16) * 16 + ((O * 4 + 15) / 16) * 16 + 256;
-}
-
-// per-env list of dead-body cells (without a map obstacle) the encoder patches; an env with more takes
-// the per-word scan
-#define PATCH_DEAD_CAP 256
-__host__ __device__ constexpr int patch_enc_bytes(int DW, int O) {  // dead words, present words, dead list, list
-    return ((DW * 4 + 15) / 16) * 16 + 256 + 4 * PATCH_DEAD_CAP + 16 + patch_list_bytes(O);
-}
-__host__ __device__ constexpr int patch_wave_bytes(int DW, int O, int slot) { return patch_enc_bytes(DW, O) + slot; }
+// (LDS sizes: patch_static_bytes, patch_enc_bytes, patch_wave_bytes, zs_obs_plan.hpp)
 
 // Stage the static tables into the workgroup's LDS (all threads, then a barrier): the padded table,
 // the obstacles' packed cells, and per lane the Box bits of its obstacles lane + 64 i.
@@ -1134,9 +1112,6 @@ struct PatchEnc {
     }
 };
 
-// waves per workgroup: eight share one copy of the static tables (16 KB at bridge64), two workgroups
-// per CU
-#define PATCH_WPG 8
 template <typename T, int NOBS>
 __global__ void __launch_bounds__(64 * PATCH_WPG, ZS_OBS_PIPE_WAVES) k_obs_patch(Dev d, T* out, int env0, int env1) {
     if (blockIdx.x == 0 && threadIdx.x == 0) step_tail(d);  // a zs_step's tail (Dev::tail_*)
@@ -1205,32 +1180,13 @@ __global__ void __launch_bounds__(64 * PATCH_WPG, ZS_OBS_PIPE_WAVES) k_obs_patch
 // u first waits for 2(u - slots) + 2.  Both sides walk upwards, so the smallest unencoded env always
 // has its slot drained eventually: no wait cycle.  Every wave leaves after its last env.
 // ---------------------------------------------------------------------------
-#ifndef RING_ENC
-#define RING_ENC 12
-#endif
-#ifndef RING_WRT
-#define RING_WRT 3  // measured on one MI355X at C3 (2 runs each): 3 writers 267.7 / 269.0 us, 4: 273.4 / 274.4, 2: 282.8 / 283.6
-#endif
-#ifndef RING_SLOTS
-#define RING_SLOTS 8
-#endif
+// (RING_ENC, RING_WRT, RING_SLOTS, ring_pair, ring_lds_bytes: zs_obs_plan.hpp)
 #ifndef RING_THR
 #define RING_THR 16
 #endif
 #ifndef ZS_RING_PF
 #define ZS_RING_PF 2  // encoder prefetch depth (items)
 #endif
-// Envs per ring unit: two when one env's block ends off a 16-B boundary and two end on one (C5's
-// int16 10 584-B envs): a unit is then one aligned, contiguous stream, with no partial 16-B chunk
-// shared by two writers.
-__host__ __device__ constexpr int ring_pair(int tsize, int nobs) {
-    return (nobs * 3 * 441 * tsize) % 16 != 0 && (2 * nobs * 3 * 441 * tsize) % 16 == 0 ? 2 : 1;
-}
-__host__ __device__ constexpr int ring_lds_bytes(int stat_bytes, int img_bytes, int tsize, int nobs) {
-    return stat_bytes + RING_ENC * img_bytes +
-           (RING_SLOTS / ring_pair(tsize, nobs)) * obs_stage_slot_bytes(tsize, nobs * ring_pair(tsize, nobs)) +
-           16 * RING_SLOTS;
-}
 
 // The hand-off is LDS-only: a wave's LDS operations complete in order, so waiting for its own LDS
 // traffic (lgkmcnt(0)) before the state store orders the slot's data before the state, and a reader's
@@ -1403,23 +1359,10 @@ __global__ void __launch_bounds__(64 * (RING_ENC + RING_WRT), 1) k_obs_ring(Dev 
 // units out as 16-B stores, as in k_obs_ring.  Unit slots: as many as fit beside the tables and the
 // encoder regions (us, at most 8 / PAIR; 5 for city128's 42-KB int64 envs).
 // ---------------------------------------------------------------------------
-// measured at C4 on one MI355X (2 runs each, profiles/r04_ab_c4_*.log): 9 / 3 159.5-159.9 us, 8 / 4 164.5,
-// 8 / 3 170, 5 / 3 184-202, 12 / 3 (4 slots) 201; with the 63-lane cell walk 9 / 3 158.3-159.7, 10 / 2
-// 153.6-155.0 (profiles/r04_ab_c4_enc.log)
-#ifndef BRING_ENC
-#define BRING_ENC 10
-#endif
-#ifndef BRING_WRT
-#define BRING_WRT 2
-#endif
+// (BRING_ENC, BRING_WRT, BRING_D, BRING_O and the LDS sizes: zs_obs_plan.hpp)
 #ifndef BRING_THR
 #define BRING_THR RING_THR
 #endif
-#define BRING_D 8  // dead-body words per lane (DW <= 512)
-#define BRING_O 2  // obstacle-present words per lane (OW <= 128, O <= 4096)
-__host__ __device__ constexpr int bring_unit_bytes(int tsize, int nobs) {
-    return obs_stage_slot_bytes(tsize, nobs * ring_pair(tsize, nobs));
-}
 __device__ __forceinline__ uint32_t chunk_of(uint32_t x, uint32_t m32) { return m32 ? __umulhi(x, m32) : x; }
 
 // ---------------------------------------------------------------------------
@@ -1432,13 +1375,6 @@ __device__ __forceinline__ uint32_t chunk_of(uint32_t x, uint32_t m32) { return 
 // first form, which built per env a map of the thing on every window cell and looked it up per cell:
 // 157.7 against 151.1 us at C4, profiles/r05f_ab_pbring.log.)
 // ---------------------------------------------------------------------------
-__host__ __device__ constexpr int pbring_enc_bytes(int DW, int OW) { return ((DW * 4 + 15) / 16) * 16 + ((OW * 4 + 15) / 16) * 16; }
-__host__ __device__ constexpr int pbring_fixed_bytes(int DW, int OW) { return 16 * DW + BRING_ENC * pbring_enc_bytes(DW, OW) + 128; }
-__host__ __device__ constexpr int pbring_slots(int DW, int OW, int tsize, int nobs, int budget) {
-    return (budget - pbring_fixed_bytes(DW, OW)) / bring_unit_bytes(tsize, nobs) < 8 / ring_pair(tsize, nobs)
-               ? (budget - pbring_fixed_bytes(DW, OW)) / bring_unit_bytes(tsize, nobs)
-               : 8 / ring_pair(tsize, nobs);
-}
 
 template <typename T, int NOBS>
 __global__ void __launch_bounds__(64 * (BRING_ENC + BRING_WRT), 1) k_obs_pbring(Dev d, T* out, int env0, int env1, int us) {

@@ -9,6 +9,7 @@ test_fullsize_parity.py.
 import numpy as np
 import pytest
 
+import obs_plan_table
 from libzombsole_amd import _abi
 from libzombsole_amd import actions as A
 
@@ -20,7 +21,9 @@ def _rich_triples(seed, step, n_agents):
 
 
 def run_parity(make_builder, n_envs, steps, stream="discrete", seed0=1000, n_discrete=7, check_state_every=25,
-               graph=False, launch=None, lanes=0):
+               graph=False, launch=None, lanes=0, expect=None):
+    """expect: the obs_plan_table.SHAPES name of (make_builder, n_envs); describe() must then name the
+    observation kernels the table lists for it under `launch`."""
     import torch
     from libzombsole_amd.engine import Engine
     from oracle.oracle import OracleEnv
@@ -29,6 +32,12 @@ def run_parity(make_builder, n_envs, steps, stream="discrete", seed0=1000, n_dis
     if lanes:
         b.cfg.lanes_per_env = lanes
     eng = Engine(b)
+    if expect:
+        mk, n = obs_plan_table.SHAPES[expect]
+        assert obs_plan_table.shape_ints(b, launch) == obs_plan_table.shape_ints(mk(n), launch), expect
+        desc = eng.describe()
+        assert (desc["obs_kernel"], desc["obs_kernel_masked"], desc["obs_encoders"]) == \
+            obs_plan_table.expected_describe(expect, launch), (expect, launch, desc)
     kinds = [o[2] for o in eng.builder.map.obstacles]
     seeds = [seed0 + i for i in range(n_envs)]
     eng.seed(seeds)
@@ -138,7 +147,10 @@ PATHS = {
     "obs_pbring": {"fobs": -1, "obs_pipe": -1},  # window-only encoders + writer waves (k_obs_pbring)
     "obs_pipe_cells": {"obs_lds": -1},          # k_obs_pipe's per-cell stores instead of the staged flush
     "obs_lds": {"obs_lds": 1},                 # the LDS-staged store kernels at any env count
-    "obs_lds_select": {"obs_lds": 1, "obs_patch": -1},  # ... without the padded-table encoder
+    # ... without the padded tables: at C2 (int64) that is k_obs_ring with the select-chain encoders, the
+    # kernel of obs_ring_select (k_obs_lds, the staged flush without writer waves, is gone: no override
+    # reaches a staged kernel that is neither k_obs_patch nor k_obs_ring)
+    "obs_lds_select": {"obs_lds": 1, "obs_patch": -1},
     "obs_ring": {"obs_lds": 1, "obs_ring": 1},  # encoder / writer waves through an LDS ring
     "obs_ring_select": {"obs_lds": 1, "obs_ring": 1, "obs_ring_patch": -1},  # ... select-chain encoders
     "obs_scan": {"obs_win": -1},                # per-cell entity scan instead of the window map
@@ -150,14 +162,27 @@ PATHS = {
 }
 
 
+# what the paths named after an observation kernel reach at C2 (describe()'s obs_kernel, obs_encoders); the
+# city_for_safehouse leg (world scope) runs k_obs under every one of them
+C2_OBS_KERNEL = {"obs_in_step": ("step launch", ""), "obs_in_step_unfused": ("step launch", ""),
+                 "obs_k_obs": ("k_obs", ""), "obs_gather": ("k_obs_gather", ""), "obs_gather_scell": ("k_obs_gather", ""),
+                 "obs_pbring": ("k_obs_pbring", ""), "obs_pipe_cells": ("k_obs_pipe", ""),
+                 "obs_lds": ("k_obs_ring", "patched"), "obs_lds_select": ("k_obs_ring", "select"),
+                 "obs_ring": ("k_obs_ring", "patched"), "obs_ring_select": ("k_obs_ring", "select")}
+
+
 @pytest.mark.parametrize("path", sorted(PATHS))
 def test_kernel_paths(path):
-    run_parity(c2, 96, 60, check_state_every=30, launch=PATHS[path])
+    if path in C2_OBS_KERNEL:
+        assert obs_plan_table.expected_describe("c2@96", PATHS[path])[::2] == C2_OBS_KERNEL[path]
+        assert obs_plan_table.expected_describe("cityfs_world@16", PATHS[path])[0] == "k_obs"
+    obs_path = any(k.startswith("obs_") or k == "fobs" for k in PATHS[path])  # the table's rows
+    run_parity(c2, 96, 60, check_state_every=30, launch=PATHS[path], expect="c2@96" if obs_path else None)
     run_parity(lambda n: _abi.single_env_config(n, "safehouse", ["terminator"], "city_for_safehouse", "0",
                                                 initial_zombies=20, minimum_zombies=20,
                                                 observation_scope="world", observation_position_encoding="channels",
                                                 max_episode_steps=50),
-               16, 60, check_state_every=30, launch=PATHS[path])
+               16, 60, check_state_every=30, launch=PATHS[path], expect="cityfs_world@16" if obs_path else None)
 
 
 # Zombie respawn in the tick's leader or deferred to k_respawn (wave per env): both bit-exact, on a
@@ -211,24 +236,33 @@ def test_step_graph(path):
                16, 30, check_state_every=15, graph=True, launch=GRAPH[path])
 
 
-@pytest.mark.parametrize("kernel", ["patch", "ring_select"])
+# name -> (launch overrides, the kernel and the encoders they select)
+STORE_STREAM = {"patch": {"obs_lds": 1, "obs_patch": 1, "obs_ring": -1},
+                "ring_select": {"obs_lds": 1, "obs_ring": 1, "obs_ring_patch": -1}}
+STORE_STREAM_KERNEL = {"patch": ("k_obs_patch", ""), "ring_select": ("k_obs_ring", "select")}
+
+
+@pytest.mark.parametrize("kernel", sorted(STORE_STREAM))
 def test_store_stream_every_phase(kernel):
     """k_obs_patch and k_obs_ring (here with its select-chain encoders) write each observation block from an
     LDS slot kept at the destination's 16-B phase: int16 blocks of 4 agents (2646 B: every even phase), int32
     single-agent blocks (5292 B)."""
-    lo = {"patch": {"obs_lds": 1, "obs_patch": 1, "obs_ring": -1},
-          "ring_select": {"obs_lds": 1, "obs_ring": 1, "obs_ring_patch": -1}}[kernel]
+    lo = STORE_STREAM[kernel]
+    for shape in ("c5@64", "bridge64_single_i32@64"):  # the table names the kernel the test is about
+        full, _, enc = obs_plan_table.expected_describe(shape, lo)
+        assert (full, enc) == STORE_STREAM_KERNEL[kernel], shape
     run_parity(lambda n: _abi.multi_env_config(n, "extermination", [], "bridge64", ["0", "1", "2", "3"],
                                                initial_zombies=20, obs_dtype=_abi.DTYPE_I16, max_episode_steps=200),
-               64, 60, check_state_every=30, launch=lo)
+               64, 60, check_state_every=30, launch=lo, expect="c5@64")
     run_parity(lambda n: _abi.single_env_config(n, "extermination", [], "bridge64", 0, initial_zombies=10,
                                                 observation_scope="surroundings:21",
                                                 observation_position_encoding="channels", max_episode_steps=200),
-               64, 60, n_discrete=6, check_state_every=30, launch=lo)
+               64, 60, n_discrete=6, check_state_every=30, launch=lo, expect="bridge64_single_i32@64")
 
 
 CITY128_OBS = {"pbring": {}, "gather": {"obs_ring": -1},
                "gather_scell": {"obs_ring": -1, "obs_gather_stat": -1}}
+CITY128_KERNEL = {"pbring": "k_obs_pbring", "gather": "k_obs_gather", "gather_scell": "k_obs_gather"}
 
 
 @pytest.mark.parametrize("path", sorted(CITY128_OBS))
@@ -236,9 +270,10 @@ def test_city128_obs_paths(path):
     """C4's observation kernels: k_obs_pbring (default: window-only encoders, the things written over the
     windows, writer waves), k_obs_gather with static words from the LDS tables or one global load per window
     cell."""
+    assert obs_plan_table.expected_describe("c4@24", CITY128_OBS[path])[0] == CITY128_KERNEL[path]
     run_parity(lambda n: _abi.multi_env_config(n, "safehouse", [], "city128", ["0", "1", "2", "3"],
                                                initial_zombies=50, minimum_zombies=50),
-               24, 30, check_state_every=15, launch=CITY128_OBS[path])
+               24, 30, check_state_every=15, launch=CITY128_OBS[path], expect="c4@24")
 
 
 @pytest.mark.parametrize("lanes", [4, 8, 16, 32, 64])
@@ -331,4 +366,50 @@ def test_masked_reset_of_pending_envs(fused, graph):
         for k in range(0, n, 17):  # pending envs included: the terminal world until the next call
             assert eng.get_state(k).canonical(kinds) == refs[k].state(), ("state", k, t)
     assert masked_pending > 0  # the masked resets met envs whose autoreset was pending
+    eng.close()
+
+
+@pytest.mark.parametrize("shape", ["c2@67", "c4@9"])
+def test_masked_observe(shape):
+    """zs_observe with an env mask runs the plan's masked kernel (describe()["obs_kernel_masked"]: k_obs on
+    bridge64, k_obs_gather on city128, whatever streams the unmasked launches): the masked envs' blocks equal
+    the oracle's observation, every other env's block is left as it was.  67 envs: odd, and no multiple of the
+    four waves of a workgroup."""
+    import torch
+    from libzombsole_amd.engine import Engine
+    from oracle.oracle import OracleEnv
+
+    mk, n = obs_plan_table.SHAPES[shape]
+    eng = Engine(mk(n))
+    assert eng.describe()["obs_kernel_masked"] == obs_plan_table.expected_describe(shape, {})[1]
+    seeds = [4100 + i for i in range(n)]
+    eng.seed(seeds)
+    eng.reset()
+    refs = []
+    for s in seeds:
+        o = OracleEnv(mk(1))
+        o.seed(s)
+        o.reset()
+        refs.append(o)
+    need = [False] * n
+    for t in range(1, 11):
+        eng.gen_actions(t, 7)
+        acts = eng.actions.cpu().numpy()
+        eng.step()
+        for k, o in enumerate(refs):
+            if need[k]:
+                o.reset()
+                need[k] = False
+            else:
+                _, _, d, tr, _ = o.step(acts[k])
+                need[k] = d or tr
+    sentinel = -12345
+    eng.obs.fill_(sentinel)
+    mask = (torch.arange(n, device=eng.device) % 3 == 0).to(torch.uint8)
+    got = eng.observe(mask).cpu().numpy()
+    for k, o in enumerate(refs):
+        if k % 3 == 0:
+            assert np.array_equal(got[k], o.obs()), ("masked obs", k)
+        else:
+            assert (got[k] == sentinel).all(), ("unmasked env written", k)
     eng.close()

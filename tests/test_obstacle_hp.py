@@ -11,6 +11,7 @@ pins the same map and actions through test_engine_golden / test_dropin_golden / 
 import numpy as np
 import pytest
 
+import obs_plan_table
 from libzombsole_amd import _abi
 from libzombsole_amd import actions as A
 from libzombsole_amd.maps import Map
@@ -56,11 +57,15 @@ def _poke_all(eng, pokes):
         eng.set_state(k, st)
 
 
-# observation kernels: the engine's pick for the size (int16: k_obs_ring, int32: k_obs_patch), the
-# store streams forced at 64 envs (int64 too: k_obs_patch, k_obs_ring), and k_obs_pipe's per-cell stores
+# observation kernels: the engine's pick for the size (int16: k_obs_ring, int32: k_obs_patch, int64:
+# k_obs_pipe), the store streams forced at 64 envs (int64 too: k_obs_patch, k_obs_ring), and k_obs_pipe's
+# per-cell stores
 OBS_PATHS = {"default": {}, "patch": {"obs_lds": 1, "obs_ring": -1},
              "ring": {"obs_lds": 1, "obs_ring": 1},
              "pipe_cells": {"obs_lds": -1}}
+# the kernel a path's name stands for, at every dtype (default: as the comment above says)
+OBS_PATH_KERNEL = {"patch": "k_obs_patch", "ring": "k_obs_ring", "pipe_cells": "k_obs_pipe"}
+DTYPE_NAME = {_abi.DTYPE_I64: "i64", _abi.DTYPE_I32: "i32", _abi.DTYPE_I16: "i16"}
 
 
 @pytest.mark.gpu
@@ -77,6 +82,14 @@ def test_engine_matches_oracle_across_resets(dtype, path):
     n, calls = 64, 160
     pokes = [(5, -32700), (6, -32720), (7, -32760)]
     eng = Engine(_builder(n, dtype).set_launch(OBS_PATHS[path]))
+    shape = "wall_hp_%s@64" % DTYPE_NAME[dtype]
+    assert obs_plan_table.shape_ints(eng.builder, OBS_PATHS[path]) == \
+        obs_plan_table.shape_ints(obs_plan_table.SHAPES[shape][0](n), OBS_PATHS[path])
+    desc = eng.describe()
+    assert (desc["obs_kernel"], desc["obs_kernel_masked"], desc["obs_encoders"]) == \
+        obs_plan_table.expected_describe(shape, OBS_PATHS[path]), desc
+    if path in OBS_PATH_KERNEL:
+        assert desc["obs_kernel"] == OBS_PATH_KERNEL[path]
     kinds = [o[2] for o in eng.builder.map.obstacles]
     seeds = [500 + i for i in range(n)]
     eng.seed(seeds)
@@ -287,6 +300,7 @@ ENCODERS = {"k_obs_patch": ({"obs_lds": 1, "obs_ring": -1, "obs_patch": 1}, "k_o
             "k_obs_pipe": ({"obs_lds": -1}, "k_obs_pipe"),
             "k_obs_ring": ({"obs_lds": 1, "obs_ring": 1}, "k_obs_ring"),
             "k_obs_ring_select": ({"obs_lds": 1, "obs_ring": 1, "obs_ring_patch": -1}, "k_obs_ring")}
+ENCODERS_OF = {"k_obs_patch": "", "k_obs_pipe": "", "k_obs_ring": "patched", "k_obs_ring_select": "select"}
 
 
 @pytest.mark.gpu
@@ -310,6 +324,9 @@ def test_observation_encoders_on_poked_states(dtype, kernel):
 
     eng = Engine(cfg(n).set_launch(ENCODERS[kernel][0]))
     assert eng.describe()["obs_kernel"] == ENCODERS[kernel][1]
+    assert eng.describe()["obs_encoders"] == ENCODERS_OF[kernel]
+    shape = "c5@64" if dtype == _abi.DTYPE_I16 else "c5_i64@64"
+    assert obs_plan_table.expected_describe(shape, ENCODERS[kernel][0])[::2] == (ENCODERS[kernel][1], ENCODERS_OF[kernel])
     eng.seed([900 + i for i in range(n)])
     eng.reset()
     rng = np.random.default_rng(11)
