@@ -196,7 +196,12 @@ typedef struct zs_config {
     int32_t obs_dtype;            /* ZS_DTYPE_*                                      */
     int32_t max_episode_steps;    /* 0 = none; else TimeLimit-style truncation       */
     uint32_t flags;               /* ZS_FLAG_*                                       */
-    int32_t lanes_per_env;        /* k_tick lanes per env (1..64, power of 2); 0 = auto */
+    int32_t lanes_per_env;        /* k_tick lanes per env: 1, 2, 4, 8, 16, 32 or 64; 0 = auto.  Any other
+                                   * value: zs_create returns ZS_EINVAL.  A workgroup of 64 lanes holds
+                                   * 64 / lanes_per_env envs in one LDS image of at most 64 KiB; where the
+                                   * image of the requested count does not fit even with the smallest
+                                   * optional copies, the count is doubled until it does.  zs_describe's
+                                   * "lanes_per_env" is the count the handle runs                        */
     const zs_launch* launch;      /* NULL = every launch choice automatic                 */
 } zs_config;
 

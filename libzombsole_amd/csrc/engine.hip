@@ -437,6 +437,13 @@ static int validate(const zs_config* c) {
     if (c->obs_scope == ZS_OBS_SURROUNDINGS && (c->obs_width <= 1 || c->obs_width % 2 == 0))
         return fail(ZS_EINVAL, "surroundings width must be an odd number greater than 1");
     if (c->obs_dtype < 0 || c->obs_dtype > 2) return fail(ZS_EINVAL, "bad obs dtype");
+    // the step kernels exist for these lane counts only (k_tick_g.hip); any other value would size the launch
+    // for 64 / G envs per workgroup and run a kernel that ticks another number
+    {
+        const int g = c->lanes_per_env;
+        if (g != 0 && (g < 1 || g > 64 || (g & (g - 1)) != 0))
+            return fail(ZS_EINVAL, "lanes_per_env must be 0 (automatic) or a power of two in 1..64");
+    }
     for (int i = 0; i < m.n_obstacles; i++) {
         int x = m.obstacle_xy[2 * i], y = m.obstacle_xy[2 * i + 1];
         if (x < 0 || y < 0 || x >= m.width || y >= m.height) return fail(ZS_EINVAL, "obstacle out of bounds");

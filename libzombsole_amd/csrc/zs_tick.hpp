@@ -903,6 +903,22 @@ __device__ __forceinline__ void grp_shuffle(const Dev& d, Grp& c, int n, int& po
     GX(2);
 }
 
+// Four consecutive entries, from k0 on, of one of an env's two exchange tables (G words at xs + g * G).  From
+// G = 4 on that is one aligned 16-B read inside the env's own entries.  With fewer lanes per env the four
+// words would run into the next envs' entries (and start off a 16-B boundary): the env's own entries are read
+// one by one and the others hold `none`, a value that matches no cell and no target.
+template <int G>
+__device__ __forceinline__ zs_v4i grp_read4(const li32* t, const ZS_LDS zs_v4i* tv, int k0, int none) {
+    if constexpr (G >= 4) {
+        return tv[k0 >> 2];
+    } else {
+        zs_v4i v;
+#pragma unroll
+        for (int u = 0; u < 4; u++) v[u] = k0 + u < G ? t[k0 + u] : none;
+        return v;
+    }
+}
+
 // execute the shuffled actions LPE(0..n) chunk by chunk.  Successful movers are appended to LM(nmoved..);
 // odirty is set when an obstacle was hit.  The lanes
 // exchange their actions through the env's two tables (t0, t1: one word per lane), read back four
@@ -974,10 +990,10 @@ __device__ __forceinline__ void grp_execute(const Dev& d, Grp& c, int n, int& po
         // entries to a nibble, and the earlier-lanes and valid-move conditions apply once, to the masks
         typedef typename std::conditional<G <= 32, uint32_t, unsigned long long>::type MaskT;
         MaskT depm = 0, vacm = 0;
-        constexpr int UNR = G <= 16 ? G / 4 : 2;  // whole scans up to 16 lanes; wider groups by halves of 8
+        constexpr int UNR = G < 4 ? 1 : G <= 16 ? G / 4 : 2;  // whole scans up to 16 lanes; wider groups by halves of 8
 #pragma unroll UNR
         for (int k0 = 0; k0 < mw; k0 += 4) {
-            const zs_v4i dv = t0v[k0 >> 2], sv = t1v[k0 >> 2];
+            const zs_v4i dv = grp_read4<G>(t0, t0v, k0, -1), sv = grp_read4<G>(t1, t1v, k0, -2);
             uint32_t vn = 0u, dn = 0u;
 #pragma unroll
             for (int u = 0; u < 4; u++) {
@@ -1059,7 +1075,7 @@ __device__ __forceinline__ void grp_execute(const Dev& d, Grp& c, int n, int& po
             // no-hit entry's target (0x7fffffff) matches no lane's.  The same values as the loop below.
 #pragma unroll UNR
             for (int k0 = 0; k0 < mw; k0 += 4) {
-                const zs_v4i tv = t0v[k0 >> 2], hvv = t1v[k0 >> 2];
+                const zs_v4i tv = grp_read4<G>(t0, t0v, k0, 0x7fffffff), hvv = grp_read4<G>(t1, t1v, k0, 0);
 #pragma unroll
                 for (int u = 0; u < 4; u++) {
                     const int k = k0 + u;
@@ -1072,7 +1088,7 @@ __device__ __forceinline__ void grp_execute(const Dev& d, Grp& c, int n, int& po
         } else {
 #pragma unroll UNR
         for (int k0 = 0; k0 < mw; k0 += 4) {
-            const zs_v4i tv = t0v[k0 >> 2], hvv = t1v[k0 >> 2];
+            const zs_v4i tv = grp_read4<G>(t0, t0v, k0, 0x7fffffff), hvv = grp_read4<G>(t1, t1v, k0, 0);
 #pragma unroll
             for (int u = 0; u < 4; u++) {
                 const int k = k0 + u;

@@ -60,6 +60,9 @@ def load(path):
                                        C.c_void_p, C.c_int32, C.c_void_p]
     L.zo_set_census.argtypes = [C.c_void_p, C.c_int]
     L.zo_census.argtypes = [C.c_void_p, C.c_void_p]
+    L.zo_census_ext.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    L.zo_run_hashes_census_ext.restype = C.c_int64
+    L.zo_run_hashes_census_ext.argtypes = L.zo_run_hashes_census.argtypes + [C.c_int32]
     return L
 
 
@@ -161,9 +164,9 @@ class OracleEnv(object):
         self.L.zo_set_census(self.h, int(chunk_g))
 
     def census(self):
-        out = np.zeros(len(CENSUS), dtype=np.int64)
-        self.L.zo_census(self.h, out.ctypes.data)
-        return dict(zip(CENSUS, (int(v) for v in out)))
+        out = np.zeros(len(CENSUS_EXT), dtype=np.int64)
+        self.L.zo_census_ext(self.h, out.ctypes.data, len(out))
+        return dict(zip(CENSUS_EXT, (int(v) for v in out)))
 
     def poke_obstacle_gone(self, i):
         return self.L.zo_poke_obstacle_gone(self.h, i)
@@ -189,18 +192,20 @@ HASH_R, HASH_D = 1 << 20, 1 << 21  # weight offsets of rewards / done, truncated
 CENSUS = ("enter_vacated", "same_dest", "target_moved", "target_later", "multi_hit", "hit_dead", "heal_clamp",
           "obst_int16", "lists", "lists_serial", "chunks", "max_in_chunk", "chunks_all6")
 CENSUS_CASES = CENSUS[:8]
+# ... and the further counters of zo_census_ext / zo_run_hashes_census_ext, which take the buffer's length
+CENSUS_EXT = CENSUS + ("lists_1chunk", "lists_2chunk", "serial_long", "serial_drew", "respawns")
 
 
 def run_hashes(builder, seed0, n_envs, steps, n_discrete, threads=0, reset_twice_mod=0, chunk_g=0):
     """Per env and step output hashes of the bench workload: uint64 [n_envs, steps + 1]
     (column 0 = the reset observation), see zo_run_hashes.  chunk_g > 0: also the conflict census of
-    every env summed (a dict, CENSUS), returned as (hashes, census)."""
+    every env summed (a dict, CENSUS_EXT), returned as (hashes, census)."""
     out = np.zeros((n_envs, steps + 1), dtype=np.uint64)
     if chunk_g <= 0:
         lib().zo_run_hashes(C.cast(builder.ptr(), C.c_void_p), seed0, n_envs, steps, n_discrete, threads,
                             reset_twice_mod, out.ctypes.data)
         return out
-    cen = np.zeros(len(CENSUS), dtype=np.int64)
-    lib().zo_run_hashes_census(C.cast(builder.ptr(), C.c_void_p), seed0, n_envs, steps, n_discrete, threads,
-                               reset_twice_mod, out.ctypes.data, int(chunk_g), cen.ctypes.data)
-    return out, dict(zip(CENSUS, (int(v) for v in cen)))
+    cen = np.zeros(len(CENSUS_EXT), dtype=np.int64)
+    lib().zo_run_hashes_census_ext(C.cast(builder.ptr(), C.c_void_p), seed0, n_envs, steps, n_discrete, threads,
+                                   reset_twice_mod, out.ctypes.data, int(chunk_g), cen.ctypes.data, len(cen))
+    return out, dict(zip(CENSUS_EXT, (int(v) for v in cen)))

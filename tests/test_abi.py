@@ -60,3 +60,23 @@ def test_checked_launder_build_compiles(tmp_path):
     import __graft_entry__ as ge
     subprocess.check_call([ge._hipcc()] + ge.HIPCC_FLAGS + ["-DZS_CHECK_LAUNDER", "-c", "-o", str(tmp_path / "k_reset.o"),
                                                          os.path.join(ge.CSRC, "k_reset.hip")])
+
+
+def test_lanes_per_env_is_validated():
+    """zs_create refuses a lanes_per_env that is neither 0 nor one of the lane counts the step kernels are
+    compiled for (1, 2, 4, 8, 16, 32, 64) before it touches a device: ZS_EINVAL (a ValueError through the
+    binding) naming the field, and no handle.  Such a value used to size the launch for 64 / G envs per
+    workgroup and then run the G = 64 kernel, which ticks one: most envs were never stepped."""
+    import pytest
+
+    from libzombsole_amd import _abi
+    L = engine.load_library()
+    for lanes in (3, 6, 48, 65, 128, -1, -8):
+        b = _abi.multi_env_config(8, "extermination", [], "bridge64", ["0", "1"], initial_zombies=10,
+                                  lanes_per_env=lanes)
+        h = ctypes.c_void_p()
+        rc = L.zs_create(ctypes.cast(b.ptr(), ctypes.c_void_p), 0, ctypes.byref(h))
+        assert rc == _abi.ZS_EINVAL and not h.value, (lanes, rc)
+        assert b"lanes_per_env" in L.zs_last_error()
+        with pytest.raises(ValueError, match="lanes_per_env"):
+            engine._raise(L, rc, "zs_create")

@@ -23,7 +23,8 @@ def _rich_triples(seed, step, n_agents):
 def run_parity(make_builder, n_envs, steps, stream="discrete", seed0=1000, n_discrete=7, check_state_every=25,
                graph=False, launch=None, lanes=0, expect=None):
     """expect: the obs_plan_table.SHAPES name of (make_builder, n_envs); describe() must then name the
-    observation kernels the table lists for it under `launch`."""
+    observation kernels the table lists for it under `launch`.  lanes: the lanes per env to request; describe()
+    must report that count (choose_layout() raises a requested count whose LDS image does not fit)."""
     import torch
     from libzombsole_amd.engine import Engine
     from oracle.oracle import OracleEnv
@@ -32,6 +33,8 @@ def run_parity(make_builder, n_envs, steps, stream="discrete", seed0=1000, n_dis
     if lanes:
         b.cfg.lanes_per_env = lanes
     eng = Engine(b)
+    if lanes:
+        assert eng.describe()["lanes_per_env"] == lanes, eng.describe()
     if expect:
         mk, n = obs_plan_table.SHAPES[expect]
         assert obs_plan_table.shape_ints(b, launch) == obs_plan_table.shape_ints(mk(n), launch), expect
@@ -287,7 +290,7 @@ def test_lanes_per_env(lanes):
                                                ["0", "1", "2"], initial_zombies=12, minimum_zombies=8,
                                                agent_weapons=["shotgun", "gun", "axe"], max_episode_steps=60,
                                                lanes_per_env=lanes),
-               48, 80, stream="rich", check_state_every=40)
+               48, 80, stream="rich", check_state_every=40, lanes=lanes)
 
 
 def test_rng_window_reload():
