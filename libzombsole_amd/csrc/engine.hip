@@ -309,10 +309,8 @@ struct zs_handle {
     zs_launch ov;   // launch overrides (zs_config.launch, zeroed when NULL)
     int device;
     Dev d;
-    int G;          // lanes per env in k_tick
-    int tick_waves = ZS_STEP_WAVES;  // k_tick's register budget (waves per SIMD it is compiled for)
-    size_t lds;     // k_tick dynamic LDS bytes
     ObsPlan obs;    // the observation kernels of an unmasked and of a masked launch (zs_obs_plan.hpp)
+    StepPlan step;  // the step, reset and respawn launches (zs_step_plan.hpp)
     // zs_step_graph: one captured hipGraph per autoreset-list parity (the step alternates the two
     // pending-reset lists), replayed on the caller's stream; keyed by the caller's buffers
     // a few buffer sets cached (a caller alternating double-buffered outputs, vector.StepGather)
@@ -327,7 +325,7 @@ struct zs_handle {
     uint64_t* d_gstep = nullptr;  // [0] policy step counter (the step's policy reads it, the step's tail advances it)
     int graph_pol = 0;            // zs_step_graph is capturing a step with this policy (n_discrete), else 0
     // next-step reset work on a side stream, concurrent with the tick (the two touch disjoint envs);
-    // the caller's stream joins it before the observations
+    // the caller's stream joins it before the observations (step.side_stream, and the stream exists)
     int reset_side = 0;
     hipStream_t s_reset = nullptr;
     hipEvent_t ev_rfork = nullptr, ev_rjoin = nullptr;
@@ -340,10 +338,6 @@ struct zs_handle {
     int* d_rlist[2];
     int* d_rcount;  // [2]
     int rpar = 0;
-    size_t reset_lds = 0;
-    int fused = 0;  // zs_step runs reset work and the tick in one launch (k_step)
-    int resident = 0;  // step-launch workgroups resident per CU (layout choice)
-    int want = 0;      // workgroups per CU the launch has (capped at 32)
     // the drop-ins' per-call path (zs_host_*), set up by its first call: one pinned, device-mapped input
     // block (actions, then the `random` state as rings + st words) the kernels read in place, one pinned,
     // device-mapped record block k_host_pack writes in place, one synchronisation per call
@@ -423,8 +417,8 @@ extern "C" int zs_destroy(zs_handle* h) {
 }
 
 static int validate(const zs_config* c) {
-    const zs_map_desc& m = c->map;
     if (!c || c->num_envs < 1) return fail(ZS_EINVAL, "num_envs must be >= 1");
+    const zs_map_desc& m = c->map;
     if (m.width < 1 || m.height < 1 || m.width > 16000 || m.height > 16000 || (long)m.width * m.height > (1L << 24))
         return fail(ZS_EINVAL, "map size out of range");
     if (c->num_agents < 1) return fail(ZS_EINVAL, "at least one agent is required");
@@ -465,66 +459,6 @@ static int validate(const zs_config* c) {
     for (int p = 0; p < c->num_bots; p++)
         if (c->bot_types[p] < ZS_BOT_TERMINATOR || c->bot_types[p] > ZS_BOT_RANDOMAN) return fail(ZS_EINVAL, "bad bot type");
     return ZS_OK;
-}
-
-// Layout of the step launch.  Workgroups of the launch resident at once on the 256 CUs decide how
-// much LDS one may take: among the layouts that fit 64 KiB, take the one with the most resident
-// workgroups (at most 32 one-wave workgroups per CU), then the largest optional LDS copies (RNG
-// window beyond 64 words, spawn candidates, spawn lists).  A fused launch (reset work + tick in
-// one) allocates max(tick image, reset image) for every workgroup.
-// reset-work workgroups of a fused step launch (zs_launch.reset_wgs overrides)
-static int reset_wgs(const zs_handle* h) { return h->ov.reset_wgs > 0 ? h->ov.reset_wgs : 256; }
-
-static int choose_layout(zs_handle* h, int want_g, bool fused, int obs_bytes) {
-    Dev& d = h->d;
-    const int kMax = 64 * 1024;
-    // A launch of many resident rounds is bound by the envs it keeps in flight per CU (k_tick at C3:
-    // 19 -> 15 resident workgroups of G = 8 took the launch from 121 to 153 us), a one-round launch by
-    // the latency of one workgroup.  Measured on one MI355X: G = 8 beats 16 when G = 16 needs more
-    // than two rounds (C3, 65536 envs, E = 12: 121 vs 140 us), G = 16 beats 8 at 8192 and 16384 envs
-    // and at C5 (E = 24); G = 32 beats 16 at C4 (E = 54: the decisions spread over more lanes).
-    // one-wave workgroups per CU the register budget admits (k_step's or k_tick's)
-    const int wave_cap = 4 * (fused ? ZS_FUSED_WAVES : ZS_STEP_WAVES);
-    int g0 = want_g > 0 ? want_g : (d.E > 32 ? 32 : 16);
-    if (want_g <= 0 && d.E <= 16 && (long)d.N > 2L * wave_cap * 256 * (64 / 16)) g0 = 8;
-    int cand_full = (d.W * d.H <= 65535) ? d.ncand : 0;
-    // RNG window: a plain step draws about 1.5 words per actor (shuffle) plus one per attack or heal
-    // in range; a window that runs dry sends the leader to HBM.  Measured with the oracle (uniform
-    // Discrete(7) agents): C3 (E = 12) mean 12, p99 26, max 37 words; C5 (E = 24) mean 23, p99 46,
-    // max 63; C4 (E = 54) median 82.  2E + 8 rounded up to a power of two covers them.
-    int rw_need = 32;
-    while (rw_need < 512 && rw_need < 2 * d.E + 8) rw_need *= 2;
-    if (h->ov.rw_need > 0) rw_need = std::max(32, std::min(512, (int)h->ov.rw_need));
-    int lists = (d.nps + d.nzs <= 4096) ? d.nps + d.nzs : 0;
-    for (int G = g0; G <= 64; G *= 2) {
-        int ne = 64 / G;
-        int wgs = (d.N + ne - 1) / ne + (fused ? std::min(d.N, reset_wgs(h)) : 0);
-        int want = h->ov.lds_budget < 0 ? 1 : std::min(32, std::max(1, (wgs + 255) / 256));
-        int best_res = -1;
-        for (int pass = 0; pass < 2 && best_res < 0; pass++)  // windows below the need only if nothing else fits
-        for (int cand : {cand_full, 0})
-            for (int lst : {lists, 0})
-                for (int rw : {512, 256, 128, 64, 32}) {
-                    if (pass == 0 && rw < rw_need) continue;
-                    int bytes = tick_layout(ne, d.E, d.DW, rw, cand, lst, d.A, obs_bytes).bytes;
-                    if (fused) bytes = std::max(bytes, reset_lds_bytes(d.E, d.DW, d.ncand, lst, obs_bytes));
-                    if (bytes > kMax) continue;
-                    int res = std::min(std::min(want, wave_cap), 160 * 1024 / bytes);
-                    h->want = want;
-                    if (res > best_res) {
-                        best_res = res;
-                        h->G = G;
-                        d.rw_cap = rw;
-                        d.rw_step = std::min(rw, rw_need);
-                        d.cand_cap = cand;
-                        d.lists_cap = lst;
-                        h->lds = bytes;
-                        h->resident = res;
-                    }
-                }
-        if (best_res > 0) return ZS_OK;
-    }
-    return fail(ZS_EINVAL, "entity table / map too large for the LDS image of one env");
 }
 
 // zs_create's handle until it succeeds: an early return frees it with everything allocated so far
@@ -745,7 +679,8 @@ static int create_env_arrays(zs_handle* h, const zs_map_desc& m) {
 static int create_obs_plan(zs_handle* h, bool rank_order) {
     Dev& d = h->d;
     const ObsShape shape = {d.N, d.W, d.H, d.O, d.OW, d.DW, d.E, d.A, d.obs_scope, d.obs_enc, d.obs_w, d.obs_dtype,
-                            d.reward_mode, d.opad_n, rank_order, d.defer_respawn};
+                            d.reward_mode, d.opad_n, rank_order,
+                            step_defer_respawn(d.minimum_zombies, d.nzs, d.W * d.H, h->ov)};
     auto lds_ok = [](int kind, int nobs, int patched, int bytes, void* dtype) {
         return obs_attr(*(const int*)dtype, kind, nobs, patched, bytes) == hipSuccess;
     };
@@ -757,68 +692,27 @@ static int create_obs_plan(zs_handle* h, bool rank_order) {
     return ZS_OK;
 }
 
-// zs_create: the step launch (fused or not, lanes per env, LDS copies), the reset launch's image and
-// the side stream of an unfused step's reset work
-static int create_step_layout(zs_handle* h) {
+// zs_create: the step plan (zs_step_plan.hpp) and what of it needs HIP: k_reset's LDS limit raised, the side
+// stream of an unfused step's reset work
+static int create_step_plan(zs_handle* h) {
     Dev& d = h->d;
-    // Fused step launch (reset work + tick in one) when the whole launch is resident at once: then
-    // the step is one latency-bound round and the reset work hides under the ticks (measured: 8192
-    // envs, 1 round, fused 0.097 ms vs 0.13 ms).  With many rounds per CU (65536 envs) the reset
-    // image and the reset role's registers cost every tick workgroup occupancy, so the reset work
-    // runs as its own short launch (0.54 ms vs 0.59 ms).  zs_launch.fused forces either.
-    {
-        const int obs_b = d.fobs ? d.obsl.bytes + 4 * d.obs_stat : 0;
-        TRY(choose_layout(h, h->cfg.lanes_per_env, true, obs_b));
-        // 8 lanes per env when 16 would take the fused launch past one resident round and 8 take fewer rounds
-        // (C3 on one MI355X: 16 384 envs, G = 16 two rounds 133.6 M env-steps/s, G = 8 one round 148.8 M;
-        // 24 576 envs fused, G = 16 140.3 M, G = 8 143.5 M; 8 192 envs stay at G = 16, one round either way;
-        // profiles/r05c_mid_sizes.log)
-        if (h->cfg.lanes_per_env <= 0 && h->G == 16 && d.E <= 16 && h->resident < h->want) {
-            const int r16 = (h->want + h->resident - 1) / h->resident;
-            TRY(choose_layout(h, 8, true, obs_b));
-            if ((h->want + h->resident - 1) / h->resident >= r16) TRY(choose_layout(h, 16, true, obs_b));
-        }
-        // up to two resident rounds the fused launch still wins: the side-stream reset work outlasts the tick
-        // (C3 16 384 envs: k_tick 38 us, k_reset 43 us) and the fused launch hides it under the ticks (C3 on one
-        // MI355X, fused against side stream: 12 288 envs 137.2 / 129.5 M, 16 384 133.1 / 123.7, 32 768 155.3 /
-        // 153.6, 49 152 165.1 / 165.5, 65 536 172.5 / 182.0; C5 16 384 153.7 / 148.3, 32 768 186.6 / 199.3;
-        // profiles/r05c_mid_sizes.log)
-        h->fused = h->ov.fused ? h->ov.fused > 0 : 2 * h->resident >= h->want;
-        // the fused launch loads its window's first 4G words with its first load round (zs_tick.hpp EARLY): a
-        // window that size costs no round trip, and the lanes' draws then reload it less often
-        if (h->fused && h->ov.rw_need <= 0) d.rw_step = std::min(d.rw_cap, std::max(d.rw_step, 4 * h->G));
-        if (!h->fused) {
-            TRY(choose_layout(h, h->cfg.lanes_per_env, false, obs_b));
-            // k_tick's register budget: 5 waves per SIMD (96 VGPRs, 20 B of scratch per lane) unless 6 (80
-            // VGPRs, 52 B of scratch on the leader's paths) saves a round of resident workgroups.  Measured
-            // on one MI355X: C3 tick 95.6 -> 91.9 us and C4 185 -> 179 us at 5; C5 (16 384 workgroups:
-            // 2.7 rounds at 6 waves, 3.2 at 5) 167 -> 178 us.  zs_launch.tick_waves forces either.
-            const int wgs = (d.N + 64 / h->G - 1) / (64 / h->G);
-            const int lres = std::max(1, 160 * 1024 / (int)h->lds);
-            auto rounds = [&](int w) {
-                const int r = std::min(lres, 4 * w);
-                return (wgs + 256 * r - 1) / (256 * r);
-            };
-            h->tick_waves = rounds(5) <= rounds(6) ? 5 : 6;
-            if (h->ov.tick_waves > 0) h->tick_waves = h->ov.tick_waves == 5 ? 5 : 6;
-            h->resident = std::min(h->resident, 4 * h->tick_waves);
-        }
-        // the reset launch stages the static spawn lists whenever they fit (no serial global loads in
-        // its candidate filters); a fused launch shares the tick's choice
-        d.rlists_cap = d.lists_cap;
-        if (!h->fused && d.nps + d.nzs <= 4096 &&
-            reset_lds_bytes(d.E, d.DW, d.ncand, d.nps + d.nzs, obs_b) <= 64 * 1024 && h->ov.reset_lists >= 0)
-            d.rlists_cap = d.nps + d.nzs;
-        h->reset_lds = (size_t)reset_lds_bytes(d.E, d.DW, d.ncand, d.rlists_cap, obs_b);
-    }
-    if (h->reset_lds > 160 * 1024) return fail(ZS_EINVAL, "map too large for the reset kernel's LDS image");
-    // side-stream reset work (unfused steps; zs_launch.reset_stream keeps it on the caller's stream)
-    if (!h->fused && h->ov.reset_stream >= 0) {
+    const StepShape shape = {d.N, d.W, d.H, d.E, d.A, d.DW, d.ncand, d.nps, d.nzs, d.minimum_zombies, h->cfg.lanes_per_env,
+                             d.fobs ? d.obsl.bytes + 4 * d.obs_stat : 0};
+    const StepPlan& p = h->step = step_plan(shape, h->ov);
+    if (p.error) return fail(ZS_EINVAL, p.error);
+    d.rw_cap = p.rw_cap;
+    d.rw_step = p.rw_step;
+    d.cand_cap = p.cand_cap;
+    d.lists_cap = p.lists_cap;
+    d.rlists_cap = p.rlists_cap;
+    d.defer_respawn = p.defer_respawn;
+    if (p.reset_lds > 160 * 1024) return fail(ZS_EINVAL, "map too large for the reset kernel's LDS image");
+    if (p.side_stream) {
         h->reset_side = hipStreamCreateWithFlags(&h->s_reset, hipStreamNonBlocking) == hipSuccess &&
                         hipEventCreateWithFlags(&h->ev_rfork, hipEventDisableTiming) == hipSuccess &&
                         hipEventCreateWithFlags(&h->ev_rjoin, hipEventDisableTiming) == hipSuccess;
     }
-    if (h->reset_lds > 64 * 1024 && reset_lds_attr((int)h->reset_lds) != hipSuccess)
+    if (p.reset_lds > 64 * 1024 && reset_lds_attr(p.reset_lds) != hipSuccess)
         return fail(ZS_EHIP, "cannot raise k_reset's dynamic LDS limit");
     return ZS_OK;
 }
@@ -863,14 +757,6 @@ extern "C" int zs_create(const zs_config* cfg, int device, zs_handle** out) {
     d.initial_zombies = cfg->initial_zombies;
     d.minimum_zombies = cfg->minimum_zombies;
     d.flags = cfg->flags;
-    // zombie respawn as wave work after the tick (k_respawn) when its shuffle is long: the tick's
-    // leader would draw one word per candidate serially.  zs_launch.defer_respawn forces either.
-    {
-        const int cands = m.n_zombie_spawns ? m.n_zombie_spawns : d.W * d.H;
-        const int dr = h->ov.defer_respawn;
-        d.defer_respawn = d.minimum_zombies > 0 && (dr ? dr > 0 : cands > 64);
-    }
-
     // the shuffle and execution of a tick's actions by the env's lanes (zs_tick.hpp grp_execute) instead of
     // its leader lane alone; zs_launch.par_exec = -1 keeps the leader's serial loop (A/B, parity tests)
     d.par_exec = h->ov.par_exec >= 0;
@@ -878,14 +764,15 @@ extern "C" int zs_create(const zs_config* cfg, int device, zs_handle** out) {
     TRY(create_static_tables(h, cfg, &rank_order));
     TRY(create_env_arrays(h, m));
     TRY(create_obs_plan(h, rank_order));
-    TRY(create_step_layout(h));
+    TRY(create_step_plan(h));
     const size_t N = d.N;
     if (getenv("ZS_VERBOSE")) {
         const ObsKernel &kf = h->obs.full, &km = h->obs.masked;
-        fprintf(stderr, "zs_create: N=%d E=%d G=%d step_lds=%zu resident=%d reset_lds=%zu rw_cap=%d cand_cap=%d "
+        const StepPlan& p = h->step;
+        fprintf(stderr, "zs_create: N=%d E=%d G=%d step_lds=%d resident=%d reset_lds=%d rw_cap=%d cand_cap=%d "
                         "lists_cap=%d fused=%d fobs=%d obs_img=%d obs=%s grid=%u block=%d lds=%d masked=%s block=%d lds=%d "
                         "reset_side=%d defer_respawn=%d\n",
-                d.N, d.E, h->G, h->lds, h->resident, h->reset_lds, d.rw_cap, d.cand_cap, d.lists_cap, h->fused,
+                d.N, d.E, p.G, p.lds, p.resident, p.reset_lds, p.rw_cap, p.cand_cap, p.lists_cap, p.fused,
                 d.fobs, d.obsl.bytes, obs_kernel_name(kf.kind), obs_grid(kf, d.N), kf.block, kf.lds,
                 obs_kernel_name(km.kind), km.block, km.lds, h->reset_side, d.defer_respawn);
     }
@@ -934,6 +821,18 @@ extern "C" int zs_seed(zs_handle* h, int32_t env0, int32_t n, const uint64_t* se
     return ZS_OK;
 }
 
+// the step-kernel unit (k_tick_g.hip) of G lanes per env, by log2 G
+struct TickUnit {
+    decltype(&launch_tick_g1) launch;
+    decltype(&stamps_g1) stamps;
+};
+static const TickUnit& tick_unit(int G) {
+#define ZS_UNIT(g) {launch_tick_g##g, stamps_g##g}
+    static const TickUnit units[7] = {ZS_UNIT(1), ZS_UNIT(2), ZS_UNIT(4), ZS_UNIT(8), ZS_UNIT(16), ZS_UNIT(32), ZS_UNIT(64)};
+#undef ZS_UNIT
+    return units[__builtin_ctz((unsigned)G)];
+}
+
 static int launch_obs(zs_handle* h, void* obs, const uint8_t* mask, hipStream_t s, int env0 = 0, int env1 = -1) {
     const Dev& d = h->d;
     if (!obs) return ZS_OK;
@@ -959,14 +858,12 @@ static int launch_tick(zs_handle* h, const int32_t* actions, double* rew, uint8_
                        uint8_t* listed, uint8_t* reset_out, int* rlist, int* rcount, void* obs, hipStream_t s,
                        int env0 = 0, int env1 = -1) {
     const Dev& d = h->d;
-    const int ne = 64 / h->G;
+    const StepPlan& sp = h->step;
+    const int ne = 64 / sp.G;
     if (env1 < 0) env1 = d.N;
     unsigned grid = (unsigned)((env1 - env0 + ne - 1) / ne);
     int i0 = -1, i1 = -1;
     const int p = h->rpar;
-    // fused: the first n_reset workgroups rebuild the envs of the pending list (ended at the previous
-    // call) while the others tick every other env; the two sets of envs are disjoint
-    const int n_reset = std::min(d.N, reset_wgs(h));
     if (h->prof) HIPCHK(hipEventRecord(prof_event(h, &i0), s));
     TickArgs a;
     a.actions = actions;
@@ -980,21 +877,11 @@ static int launch_tick(zs_handle* h, const int32_t* actions, double* rew, uint8_
     a.obs = obs;
     a.env0 = env0;
     a.env1 = env1;
-    a.n_reset = h->fused ? n_reset : 0;
+    a.n_reset = sp.n_reset;
     a.cur_list = (const int*)h->d_rlist[p];
     a.cur_count = (const int*)(h->d_rcount + p);
     a.err = h->d_err;
-    hipError_t le;
-    switch (h->G) {
-    case 1: le = launch_tick_g1(h->fused, h->tick_waves, grid, h->lds, s, d, a); break;
-    case 2: le = launch_tick_g2(h->fused, h->tick_waves, grid, h->lds, s, d, a); break;
-    case 4: le = launch_tick_g4(h->fused, h->tick_waves, grid, h->lds, s, d, a); break;
-    case 8: le = launch_tick_g8(h->fused, h->tick_waves, grid, h->lds, s, d, a); break;
-    case 16: le = launch_tick_g16(h->fused, h->tick_waves, grid, h->lds, s, d, a); break;
-    case 32: le = launch_tick_g32(h->fused, h->tick_waves, grid, h->lds, s, d, a); break;
-    default: le = launch_tick_g64(h->fused, h->tick_waves, grid, h->lds, s, d, a); break;
-    }
-    HIPCHK(le);
+    HIPCHK(tick_unit(sp.G).launch(sp.fused, sp.tick_waves, grid, (size_t)sp.lds, s, d, a));
     if (h->prof) {
         HIPCHK(hipEventRecord(prof_event(h, &i1), s));
         h->ev_tick.push_back({i0, i1});
@@ -1004,13 +891,11 @@ static int launch_tick(zs_handle* h, const int32_t* actions, double* rew, uint8_
 
 static int launch_reset(zs_handle* h, int list_mode, const uint8_t* mask, void* obs, hipStream_t s) {
     const Dev& d = h->d;
-    // enough one-wave workgroups that a step's resets (~850 at 65536 envs, bridge64) run in one round
-    const int rgrid = h->ov.reset_grid > 0 ? h->ov.reset_grid : 2048;
-    unsigned grid = (unsigned)std::min(d.N, list_mode ? rgrid : 4096);
+    const unsigned grid = (unsigned)(list_mode ? h->step.reset_grid_list : h->step.reset_grid_mask);
     int p = h->rpar;
     int i0 = -1, i1 = -1;
     if (h->prof) HIPCHK(hipEventRecord(prof_event(h, &i0), s));
-    HIPCHK(launch_reset_k(grid, h->reset_lds, s, d, list_mode, h->d_rlist[p], h->d_rcount + p, mask, h->d_err, obs));
+    HIPCHK(launch_reset_k(grid, (size_t)h->step.reset_lds, s, d, list_mode, h->d_rlist[p], h->d_rcount + p, mask, h->d_err, obs));
     if (h->prof) {
         HIPCHK(hipEventRecord(prof_event(h, &i1), s));
         h->ev_reset.push_back({i0, i1});
@@ -1021,12 +906,9 @@ static int launch_reset(zs_handle* h, int list_mode, const uint8_t* mask, void* 
 // the respawns the tick just deferred (k_respawn drains d.resp_list; count zeroed before the tick)
 static int launch_respawn(zs_handle* h, hipStream_t s) {
     const Dev& d = h->d;
-    // enough one-wave workgroups for a step's respawns in one pass (C4: 2048 -> 8192 took the launch
-    // from 88 to 70 us; workgroups past the list's end exit at once)
-    const int grid = h->ov.respawn_grid > 0 ? h->ov.respawn_grid : 8192;
     int i0 = -1, i1 = -1;
     if (h->prof) HIPCHK(hipEventRecord(prof_event(h, &i0), s));
-    HIPCHK(launch_respawn_k((unsigned)std::min(d.N, grid), h->reset_lds, s, d));
+    HIPCHK(launch_respawn_k((unsigned)h->step.respawn_grid, (size_t)h->step.reset_lds, s, d));
     if (h->prof) {
         HIPCHK(hipEventRecord(prof_event(h, &i1), s));
         h->ev_respawn.push_back({i0, i1});
@@ -1090,7 +972,7 @@ extern "C" int zs_step(zs_handle* h, const int32_t* actions_dev, void* obs_dev, 
     //    when the LDS images allow, else a k_reset launch first
     int q = 1 - h->rpar, rc = ZS_OK;
     bool side = false;
-    if (!h->fused) {
+    if (!h->step.fused) {
         side = h->reset_side != 0;
         hipStream_t rs = s;
         if (side) {  // fork: the reset work sees everything the caller queued before this call
@@ -1423,14 +1305,15 @@ extern "C" int zs_describe(zs_handle* h, char* buf, int32_t len) {
     if (!h || !buf || len <= 0) return fail(ZS_EINVAL, "null argument");
     const Dev& d = h->d;
     const ObsKernel& kf = h->obs.full;
+    const StepPlan& p = h->step;
     snprintf(buf, (size_t)len,
-             "{\"envs\": %d, \"entities\": %d, \"lanes_per_env\": %d, \"step_kernel\": \"%s\", \"step_lds\": %zu, "
+             "{\"envs\": %d, \"entities\": %d, \"lanes_per_env\": %d, \"step_kernel\": \"%s\", \"step_lds\": %d, "
              "\"step_wgs_per_cu\": %d, \"rng_window\": %d, \"obs_kernel\": \"%s\", \"reset_side_stream\": %d, "
-             "\"reset_lds\": %zu, \"respawn\": \"%s\", \"tick_waves\": %d, \"rng_step\": %d, \"par_exec\": %d, "
+             "\"reset_lds\": %d, \"respawn\": \"%s\", \"tick_waves\": %d, \"rng_step\": %d, \"par_exec\": %d, "
              "\"obs_kernel_masked\": \"%s\", \"obs_encoders\": \"%s\"}",
-             d.N, d.E, h->G, h->fused ? "k_step" : "k_tick", h->lds, h->resident, d.rw_cap,
+             d.N, d.E, p.G, p.fused ? "k_step" : "k_tick", p.lds, p.resident, p.rw_cap,
              d.fobs ? "step launch" : obs_kernel_name(kf.kind), h->reset_side,
-             h->reset_lds, d.defer_respawn ? "k_respawn" : "tick", h->fused ? ZS_FUSED_WAVES : h->tick_waves, d.rw_step,
+             p.reset_lds, p.defer_respawn ? "k_respawn" : "tick", p.tick_waves, p.rw_step,
              d.par_exec, obs_kernel_name(h->obs.masked.kind), obs_encoders_name(kf));
     return ZS_OK;
 }
@@ -1634,21 +1517,6 @@ extern "C" int zs_debug_lists(zs_handle* h, int32_t* out, void* stream) {
 // ---------------------------------------------------------------------------
 // diagnostic build (-DZS_STAMPS): per-phase k_tick cycle sums since the last read
 // ---------------------------------------------------------------------------
-#ifdef ZS_STAMPS
-// this handle's step-kernel unit (its G)
-static hipError_t stamps_of(int G, unsigned long long* wg, unsigned long long* tl, int clear) {
-    switch (G) {
-    case 1: return stamps_g1(wg, tl, clear);
-    case 2: return stamps_g2(wg, tl, clear);
-    case 4: return stamps_g4(wg, tl, clear);
-    case 8: return stamps_g8(wg, tl, clear);
-    case 16: return stamps_g16(wg, tl, clear);
-    case 32: return stamps_g32(wg, tl, clear);
-    default: return stamps_g64(wg, tl, clear);
-    }
-}
-#endif
-
 // diagnostic build (-DZS_STAMPS): start / end s_memrealtime of the first n workgroups of the last step launch
 extern "C" int zs_debug_timeline(zs_handle* h, uint64_t* out, int32_t n) {
 #ifdef ZS_STAMPS
@@ -1656,7 +1524,7 @@ extern "C" int zs_debug_timeline(zs_handle* h, uint64_t* out, int32_t n) {
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipDeviceSynchronize());
     std::vector<unsigned long long> tl((size_t)ZS_STAMP_WGS * 2);
-    HIPCHK(stamps_of(h->G, nullptr, tl.data(), 0));
+    HIPCHK(tick_unit(h->step.G).stamps(nullptr, tl.data(), 0));
     std::memcpy(out, tl.data(), (size_t)n * 2 * sizeof(unsigned long long));
     return ZS_OK;
 #else
@@ -1672,7 +1540,7 @@ extern "C" int zs_debug_stamps_wg(zs_handle* h, uint64_t* out, int32_t n_wgs, in
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipDeviceSynchronize());
     std::vector<unsigned long long> buf((size_t)ZS_STAMP_WGS * ZS_NPHASE);
-    HIPCHK(stamps_of(h->G, buf.data(), nullptr, 1));
+    HIPCHK(tick_unit(h->step.G).stamps(buf.data(), nullptr, 1));
     for (int w = 0; w < n_wgs; w++)
         for (int k = 0; k < n_phase; k++) out[(size_t)w * n_phase + k] = buf[(size_t)w * ZS_NPHASE + k];
     return ZS_OK;
@@ -1689,7 +1557,7 @@ extern "C" int zs_debug_stamps(zs_handle* h, uint64_t* sum_out, uint64_t* max_ou
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipDeviceSynchronize());
     std::vector<unsigned long long> buf((size_t)ZS_STAMP_WGS * ZS_NPHASE), rb(buf.size());
-    HIPCHK(stamps_of(h->G, buf.data(), nullptr, 1));
+    HIPCHK(tick_unit(h->step.G).stamps(buf.data(), nullptr, 1));
     HIPCHK(stamps_reset(rb.data(), 1));
     for (int k = 0; k < n; k++) {
         sum_out[k] = 0;

@@ -19,27 +19,14 @@
 #include <stdint.h>
 
 #include "../../include/zombsole_mi355x.h"
-#include "zs_obs_plan.hpp"  // ObsLayout
+#include "zs_obs_plan.hpp"   // ObsLayout
+#include "zs_step_plan.hpp"  // ZS_STEP_WAVES, ZS_FUSED_WAVES, ZS_MT_N, the step launch's LDS images
 
-// minimum waves per SIMD the one-wave step / tick / reset kernels are compiled for (register budget):
-// 6 caps k_tick at 80 VGPRs (88 unbounded: 5 waves) for a few dwords of scratch on cold paths;
-// measured C3 125 -> 127, C5 109 -> 114 M env-steps/s, C4 unchanged; 8 (64 VGPRs) spills more and
-// loses at C4
-#ifndef ZS_STEP_WAVES
-#define ZS_STEP_WAVES 6
-#endif
-// The fused step launch (k_step) is chosen only when the whole launch is resident at once (at most
-// 4 * ZS_FUSED_WAVES one-wave workgroups per CU), and k_reset runs a few waves per CU beside the tick
-// (3.8 measured at C3): neither needs k_tick's occupancy, and at 6 waves both spill (k_step 244,
-// k_reset 292 bytes of scratch per lane, on their serial chains).  3 waves: 147 / 151 VGPRs, none.
-#ifndef ZS_FUSED_WAVES
-#define ZS_FUSED_WAVES 3
-#endif
+// k_reset's register budget (waves per SIMD; ZS_STEP_WAVES, ZS_FUSED_WAVES and their measurements: zs_step_plan.hpp)
 #ifndef ZS_RESET_WAVES
 #define ZS_RESET_WAVES 3
 #endif
 
-#define ZS_MT_N 624
 #define ZS_MT_M 397
 #define ZS_RING_WORDS (2 * ZS_MT_N)
 

@@ -4,7 +4,7 @@
 //   k_tick_g.hip  once per lanes-per-env G (-DZS_G=1..64): k_tick<G, 5/6> and the fused k_step<G>
 //   k_obs_t.hip   once per observation dtype (-DZS_OBS_T=0/1/2): every observation kernel
 //   k_reset.hip   k_reset, k_respawn, k_list_filter
-//   engine.hip    the C ABI, the layout choice and the small helper kernels
+//   engine.hip    the C ABI and the small helper kernels (the launches are planned in zs_obs_plan.hpp, zs_step_plan.hpp)
 // Each unit exports plain host functions that launch its kernels; nothing but Dev, the observation
 // plan's ObsKernel (zs_obs_plan.hpp) and plain pointers crosses the units.
 #pragma once

@@ -29,13 +29,6 @@ struct ResetLds {
     lu32* tw;
 };
 
-// the twist buffer doubles as the observation image of the env just rebuilt (obs_bytes)
-__host__ __device__ inline int reset_lds_bytes(int E, int DW, int ncand, int lists_cap, int obs_bytes = 0) {
-    int o = DW * 4 + ncand * 4 + 2 * E * 4 + 4 * E + lists_cap * 4 + (E + 8) * 4;
-    o = ((o + 15) / 16) * 16;
-    return o + (obs_bytes > 2 * ZS_MT_N * 4 ? obs_bytes : 2 * ZS_MT_N * 4);
-}
-
 __device__ __forceinline__ bool rbm_test(const ResetLds& L, int cell) { return (L.bm[cell >> 5] >> (cell & 31)) & 1u; }
 
 // World.spawn_in_random (core.py:40-66) for k slots in L.lslots[0..k): ballot-compacted

@@ -104,75 +104,8 @@ static __device__ unsigned long long g_stamp_tl[ZS_STAMP_WGS * 2];
 static __constant__ int c_adj_dx[4] = {0, 0, 1, -1};
 static __constant__ int c_adj_dy[4] = {1, -1, 0, 0};
 
-// LDS footprint of one workgroup (host and device agree on this layout).  The entity columns the
-// observations need (pos, life, weapon, present) sit before `region`; everything in `region` is
-// dead once the tick's state is stored, so the observation image of the env being encoded and the
-// MT twist buffer alias it.
-struct TickLayout {
-    int ne;                                  // envs per workgroup
-    int off_lists;                           // static spawn lists (player then zombie), shared by the WG
-    int off_misc;                            // per-env scalars / tracker, [MISC_*][ne] int32
-    int off_lst;
-    int off_pos, off_life, off_weap, off_pres;
-    int off_region;                          // = off_bm
-    int off_bm, off_rw, off_cand, off_tgt, off_act, off_order, off_rank, off_kind, off_perm, off_moved, off_xs;
-    int bytes;
-};
-
-// per-env LDS scalars (MISC rows); rows MISC_N.. hold prev_life[A] then listed[A].  MISC_NMOVED and
-// MISC_NORD are scratch rows of the tick's leader / group hand-off (not staged from or to HBM).
-enum { MISC_T = 0, MISC_DEATHS, MISC_ZD, MISC_EPSTEPS, MISC_PREVZD, MISC_SERIAL, MISC_ODIRTY, MISC_NMOVED, MISC_NORD, MISC_N };
-
-__host__ __device__ inline TickLayout tick_layout(int ne, int E, int DW, int rw_cap, int cand_cap, int lists_cap,
-                                                  int A, int obs_bytes = 0) {
-    TickLayout L;
-    L.ne = ne;
-    int o = 0;
-    L.off_lists = o;
-    o += lists_cap * 4;
-    L.off_misc = o;
-    o += (MISC_N + 2 * A) * ne * 4;
-    L.off_lst = o;
-    o += ne * 4;
-    L.off_pos = o;
-    o += E * ne * 4;
-    L.off_life = o;
-    o += E * ne * 4;
-    L.off_weap = o;
-    o += E * ne;
-    L.off_pres = o;
-    o += E * ne;
-    L.off_order = o;  // the dict order is stored out after the MT refill, whose buffer aliases the region
-    o += E * ne;
-    o = ((o + 15) / 16) * 16;
-    const int region = o;
-    L.off_region = L.off_bm = o;
-    o += DW * ne * 4;
-    L.off_rw = o;
-    o += rw_cap * ne * 4;
-    L.off_tgt = o;
-    o += E * ne * 4;
-    L.off_act = o;  // the agents' action triples, loaded with the stage-in round
-    o += 3 * A * ne * 4;
-    L.off_cand = o;
-    o += ((cand_cap * ne * 2 + 3) / 4) * 4;
-    L.off_rank = o;
-    o += E * ne;
-    L.off_kind = o;
-    o += E * ne;
-    L.off_perm = o;
-    o += E * ne;
-    L.off_moved = o;
-    o += E * ne;
-    o = ((o + 15) / 16) * 16;
-    L.off_xs = o;  // grp_execute's two tables of 64 words (G per env)
-    o += 2 * 64 * 4;
-    // the MT twist buffer (2 x 624 words) and one env's observation image alias the region
-    if (o - region < 2 * ZS_MT_N * 4) o = region + 2 * ZS_MT_N * 4;
-    if (o - region < obs_bytes) o = region + obs_bytes;
-    L.bytes = o;
-    return L;
-}
+// The workgroup's LDS image is TickLayout / tick_layout() and the MISC_* rows of zs_step_plan.hpp (the host's
+// launch plan sizes the same image).
 
 // one env as seen by one lane of its group
 struct Grp {

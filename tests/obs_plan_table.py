@@ -104,15 +104,15 @@ def ov_key(lo):
 
 
 def shape_ints(builder, lo):
-    """The ObsShape of a config (zs_create's arithmetic on the config's integers), in the struct's order."""
+    """The ObsShape of a config (zs_create's arithmetic on the config's integers; defer_respawn as the compiled
+    step plan decides it), in the struct's order."""
     c, m = builder.cfg, builder.cfg.map
     W, H, O = m.width, m.height, m.n_obstacles
     E = c.num_agents + c.num_bots + max(c.initial_zombies, c.minimum_zombies)
     cells = [m.obstacle_xy[2 * i + 1] * W + m.obstacle_xy[2 * i] for i in range(O)]
     rank_order = all(b > a for a, b in zip(cells, cells[1:]))
-    cands = m.n_zombie_spawns or W * H
-    dr = (lo or {}).get("defer_respawn", 0)
-    defer = c.minimum_zombies > 0 and (dr > 0 if dr else cands > 64)
+    import step_plan_table
+    defer = step_plan_table.defer_respawn(builder, lo)  # step_defer_respawn() (zs_step_plan.hpp), compiled
     return [c.num_envs, W, H, O, (O + 31) // 32, (W * H + 31) // 32, E, c.num_agents, c.obs_scope, c.obs_encoding,
             c.obs_width, c.obs_dtype, c.reward_mode, (W + 20) * (H + 20), int(rank_order), int(defer)]
 

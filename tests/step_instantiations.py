@@ -1,20 +1,21 @@
 """One case per step-kernel instantiation (libzombsole_amd/csrc/k_tick_g.hip, compiled for G = 1 .. 64 lanes per
 env): k_step<G> (reset work and tick in one launch), k_tick<G, 5> and k_tick<G, 6> (the tick alone, compiled for
 5 or 6 waves per SIMD): 21 device functions.  test_step_instantiations_plan.py checks on the CPU that the rows
-and the UNREACHABLE dict together are the 21, that the LDS image of every row's requested G fits (so the engine
-does not raise the G) and, with the oracle's census, that the rows of every G meet the action-list regimes they
+and the UNREACHABLE dict together are the 21, that the compiled step plan resolves every row to its instantiation
+(the LDS image of the requested G fits, so the plan does not raise the G) and, with the oracle's census, that the rows of every G meet the action-list regimes they
 claim; test_step_instantiations.py runs every row on the GPU.
 
-What describe() must report is written down from reading engine.hip, not produced by running it:
+What describe() must report is what the compiled step plan (libzombsole_amd/csrc/zs_step_plan.hpp, through
+tests/step_plan_dump.cpp) resolves every row's config and overrides to; test_step_instantiations_plan.py checks on
+the CPU that this is the row's G, kernel and wave budget:
 
-  * create_step_layout(): zs_launch.fused = 1 takes k_step at any env count, fused = -1 k_tick, whose register
-    budget zs_launch.tick_waves (5 or 6) then names; describe()'s "tick_waves" is ZS_FUSED_WAVES (3) for k_step;
-  * choose_layout() starts at the requested G and doubles it only while no LDS image of 64 / G envs fits 64 KiB,
-    not even the smallest one (a 32-word RNG window, no spawn-candidate copy, no spawn lists): min_image_bytes()
-    below restates tick_layout() (zs_tick.hpp) and reset_lds_bytes() (zs_reset.hpp) for that smallest image;
-  * zs_create(): respawn by k_respawn where the config keeps a minimum of zombies and the zombie spawn list (or
-    the map, without one) has more than 64 cells, by the tick otherwise; par_exec = 1 unless zs_launch.par_exec
-    is -1.
+  * zs_launch.fused = 1 takes k_step at any env count, fused = -1 k_tick, whose register budget
+    zs_launch.tick_waves (5 or 6) then names; describe()'s "tick_waves" is ZS_FUSED_WAVES (3) for k_step;
+  * the plan starts at the requested G and doubles it only while no LDS image of 64 / G envs fits 64 KiB, not even
+    the smallest one (a 32-word RNG window, no spawn-candidate copy, no spawn lists; min_image_args() below);
+  * respawn by k_respawn where the config keeps a minimum of zombies and the zombie spawn list (or the map,
+    without one) has more than 64 cells, by the tick otherwise (step_defer_respawn()); par_exec = 1 unless
+    zs_launch.par_exec is -1.
 
 Every row sets fobs = -1 (observations by the observation kernels, never by the step launch), so no observation
 image enters the step's LDS arithmetic.
@@ -167,8 +168,7 @@ _ROWS = {
 # to four actions: both paths in one workgroup), 1 of the 4 of a G = 16 one
 _SMALL = {(1, "k_step", 3): ("pen_quad", ("serial_long", "two_chunk")), (16, "k_tick6", 1): ("c2", ("one_chunk",))}
 
-# Instantiations no config reaches, each with the choose_layout() / create_step_layout() condition that excludes
-# it.  There is none: every G fits some config's image, fused = 1 / -1 forces k_step / k_tick at any env count and
+# Instantiations no config reaches, each with the step_plan() condition (zs_step_plan.hpp) that excludes it.  There is none: every G fits some config's image, fused = 1 / -1 forces k_step / k_tick at any env count and
 # tick_waves forces either register budget.
 UNREACHABLE = {}
 
@@ -232,37 +232,14 @@ def all_instantiations():
     return [(G, k) for G in GS for k in KERNELS]
 
 
-# -- the smallest LDS image of 64 / G envs (tick_layout, reset_lds_bytes) ---------------------------------------
-MT_N, MISC_N = 624, 9
-
-
-def _align16(o):
-    return (o + 15) // 16 * 16
-
-
-def tick_image_bytes(ne, E, DW, rw, cand, lists, n_agents):
-    """zs_tick.hpp tick_layout().bytes without an observation image."""
-    o = lists * 4 + (MISC_N + 2 * n_agents) * ne * 4 + ne * 4 + 2 * E * ne * 4 + 3 * E * ne
-    region = o = _align16(o)
-    o += DW * ne * 4 + rw * ne * 4 + E * ne * 4 + 3 * n_agents * ne * 4 + (cand * ne * 2 + 3) // 4 * 4 + 4 * E * ne
-    o = _align16(o) + 2 * 64 * 4
-    return max(o, region + 2 * MT_N * 4)
-
-
-def reset_image_bytes(E, DW, ncand, lists):
-    """zs_reset.hpp reset_lds_bytes() without an observation image."""
-    return _align16(DW * 4 + ncand * 4 + 2 * E * 4 + 4 * E + lists * 4 + (E + 8) * 4) + 2 * MT_N * 4
-
-
-def min_image_bytes(builder, G, fused):
-    """The smallest image choose_layout() tries for G lanes per env: 32-word window, no candidate copy, no lists."""
+def min_image_args(builder, G, fused):
+    """The arguments (step_plan_table.images) of the smallest image the plan tries for G lanes per env: a 32-word
+    RNG window, no spawn-candidate copy, no spawn lists, no observation image."""
     c, m = builder.cfg, builder.cfg.map
     E = c.num_agents + c.num_bots + max(c.initial_zombies, c.minimum_zombies)
     cells = m.width * m.height
-    DW = (cells + 31) // 32
     ncand = max(m.n_player_spawns or cells, m.n_zombie_spawns or cells)
-    b = tick_image_bytes(64 // G, E, DW, 32, 0, 0, c.num_agents)
-    return max(b, reset_image_bytes(E, DW, ncand, 0)) if fused else b
+    return (int(fused), 64 // G, E, (cells + 31) // 32, 32, 0, 0, c.num_agents, ncand, 0)
 
 
 def census(row, steps=STEPS):

@@ -24,7 +24,7 @@ def run_parity(make_builder, n_envs, steps, stream="discrete", seed0=1000, n_dis
                graph=False, launch=None, lanes=0, expect=None):
     """expect: the obs_plan_table.SHAPES name of (make_builder, n_envs); describe() must then name the
     observation kernels the table lists for it under `launch`.  lanes: the lanes per env to request; describe()
-    must report that count (choose_layout() raises a requested count whose LDS image does not fit)."""
+    must report that count (step_plan() raises a requested count whose LDS image does not fit)."""
     import torch
     from libzombsole_amd.engine import Engine
     from oracle.oracle import OracleEnv

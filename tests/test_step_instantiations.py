@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import step_instantiations as S
+import step_plan_table as T
 from libzombsole_amd import _abi
 from test_obs_instantiations import FILL, GUARD
 
@@ -153,14 +154,24 @@ def run_engines(builders, make_oracle, seeds, steps, stream_row, graph=False, st
 ALL_ROWS = S.ROWS + S.SMALL_ROWS
 
 
+def plan_describe(row):
+    """The describe() fields that the step plan decides, from the plan's table row of the row's config and overrides
+    (test_step_plan.py and test_step_instantiations_plan.py hold the compiled plan to that row on the CPU)."""
+    p = T.expected("row:" + row.id, row.launch)
+    return {"step_lds": p["lds"], "step_wgs_per_cu": p["resident"], "rng_window": p["rw_cap"], "rng_step": p["rw_step"],
+            "reset_lds": p["reset_lds"], "reset_side_stream": p["side_stream"]}
+
+
 @pytest.mark.parametrize("row", ALL_ROWS, ids=[r.id for r in ALL_ROWS])
 def test_instantiation(row):
     """One instantiation, with the lanes' execution (par_exec 1) and with the leader's serial loop (par_exec -1):
-    describe() names the requested lanes per env, the kernel and its wave budget; 24 steps of episodes of five,
+    describe() names the requested lanes per env, the kernel and its wave budget, and the LDS sizes, resident
+    workgroups, RNG window and side stream of the step plan's row; 24 steps of episodes of five,
     every env of both engines against the oracle at every step, the state at steps 12 and 24."""
     pars = (1, -1)
     resets, _ = run_engines([row.builder(par_exec=p) for p in pars], row.make, row.seeds(), S.STEPS, row,
-                            states_at=(S.STEPS // 2, S.STEPS), expect=[row.describe(p) for p in pars])
+                            states_at=(S.STEPS // 2, S.STEPS),
+                            expect=[dict(row.describe(p), **plan_describe(row)) for p in pars])
     assert sum(resets) >= 4 * row.n  # every env went through four autoresets or more
 
 

@@ -1,12 +1,14 @@
 """The case table of step_instantiations.py on the CPU: the rows and the justified unreachable entries are the 21
-device functions of k_tick_g.hip; every row's requested lanes-per-env count fits its LDS image, so choose_layout()
-(engine.hip) keeps it; the env counts give partial workgroups; and the oracle's census of every row's own config,
+device functions of k_tick_g.hip; the compiled step plan (zs_step_plan.hpp) resolves every row's config and
+overrides to the row's instantiation, and every row's requested lanes-per-env count fits its LDS image, so the
+plan keeps it; the env counts give partial workgroups; and the oracle's census of every row's own config,
 seeds, action stream and steps shows the action-list regimes and the conflict cases the rows claim."""
 import os
 
 import pytest
 
 import step_instantiations as S
+import step_plan_table as T
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "libzombsole_amd", "csrc")
@@ -20,9 +22,9 @@ def test_rows_cover_all_21():
     assert not set(rows) & set(S.UNREACHABLE)
     assert set(rows) | set(S.UNREACHABLE) == set(every)
     assert len(rows) + len(S.UNREACHABLE) == 21
-    with open(os.path.join(CSRC, "engine.hip")) as f:
+    with open(os.path.join(CSRC, "zs_step_plan.hpp")) as f:
         src = f.read()
-    for key, cond in S.UNREACHABLE.items():  # every unreachable entry quotes a condition that stands in the source
+    for key, cond in S.UNREACHABLE.items():  # every unreachable entry quotes a condition that stands in the plan
         assert cond and cond in src, key
     # launches of less than one workgroup: one per kernel kind
     assert {r.step_kernel for r in S.SMALL_ROWS} == {"k_step", "k_tick"}
@@ -30,37 +32,38 @@ def test_rows_cover_all_21():
     assert len({r.id for r in S.ROWS + S.SMALL_ROWS}) == len(S.ROWS) + len(S.SMALL_ROWS)
 
 
-def test_overrides_are_the_ones_the_layout_reads():
-    """The conditions the table's expectations were written from still stand in create_step_layout() /
-    choose_layout() / zs_describe()."""
-    with open(os.path.join(CSRC, "engine.hip")) as f:
-        src = f.read()
-    for cond in ("h->fused = h->ov.fused ? h->ov.fused > 0 :",
-                 "if (h->ov.tick_waves > 0) h->tick_waves = h->ov.tick_waves == 5 ? 5 : 6;",
-                 "for (int G = g0; G <= 64; G *= 2) {",
-                 "if (bytes > kMax) continue;",
-                 "h->fused ? ZS_FUSED_WAVES : h->tick_waves",
-                 "d.defer_respawn = d.minimum_zombies > 0 && (dr ? dr > 0 : cands > 64);",
-                 "d.par_exec = h->ov.par_exec >= 0;"):
-        assert cond in src, cond
-    with open(os.path.join(CSRC, "zs_device.hpp")) as f:
-        assert "#define ZS_FUSED_WAVES 3" in f.read()
-    for r in S.ROWS + S.SMALL_ROWS:
+ALL_ROWS = S.ROWS + S.SMALL_ROWS
+
+
+def test_the_plan_resolves_every_row_to_its_instantiation():
+    """The compiled step plan, given every row's config and overrides, names the row's lanes per env, kernel and
+    wave budget (what describe() must report), and step_defer_respawn() the row's respawn."""
+    plans = T.plans([(r.builder(), dict(r.launch, par_exec=1)) for r in ALL_ROWS])
+    for r, p in zip(ALL_ROWS, plans):
+        assert "error" not in p, (r.id, p)
+        assert (p["G"], bool(p["fused"]), p["tick_waves"]) == (r.G, r.fused, r.tick_waves), (r.id, p)
+        assert ("k_step" if p["fused"] else "k_tick") == r.step_kernel == r.describe()["step_kernel"], r.id
+        assert ("k_respawn" if p["defer_respawn"] else "tick") == r.respawn, (r.id, p)
+        assert T.defer_respawn(r.builder(), r.launch) == p["defer_respawn"], r.id
+        assert p["obs_bytes"] == 0, (r.id, p)  # fobs = -1: no observation image in the step's LDS
         assert r.launch["fobs"] == -1 and r.launch["fused"] == (1 if r.fused else -1)
         assert r.launch.get("tick_waves", 0) == (0 if r.fused else r.tick_waves)
         assert r.describe()["tick_waves"] == (3 if r.fused else int(r.kernel[-1]))
+        assert {k: p[k] for k in T.FIELDS} == {k: T.expected("row:" + r.id, r.launch)[k] for k in T.FIELDS}, r.id
 
 
 def test_requested_lanes_fit_their_image():
-    """choose_layout() raises a requested G only when not even the smallest image of 64 / G envs fits 64 KiB."""
-    for r in S.ROWS + S.SMALL_ROWS:
-        b = r.builder(1)
-        assert S.min_image_bytes(b, r.G, r.fused) <= 64 * 1024, (r.id, S.min_image_bytes(b, r.G, r.fused))
+    """The plan raises a requested G only when not even the smallest image of 64 / G envs fits 64 KiB."""
+    def min_bytes(builder, G, fused):
+        return T.images([S.min_image_args(builder, G, fused)])[0]["bytes"]
+    sizes = T.images([S.min_image_args(r.builder(1), r.G, r.fused) for r in ALL_ROWS])
+    for r, im in zip(ALL_ROWS, sizes):
+        assert im["bytes"] <= 64 * 1024, (r.id, im)
     # the arithmetic bites: city128's bitmap alone (512 words an env) fills 64 KiB with 32 envs, so the city128
     # rows start at G = 16; and bridge64's 12 entities leave 64 envs to an image little room (the c2 row of G = 1)
-    assert S.min_image_bytes(S.c4(1), 1, False) > S.min_image_bytes(S.c4(1), 2, False) > 64 * 1024
-    assert S.min_image_bytes(S.c4(1), 4, True) <= 64 * 1024
-    assert 56 * 1024 < S.min_image_bytes(S.c2(1), 1, False) <= 64 * 1024 < S.min_image_bytes(S.c5(1), 1, False)
+    assert min_bytes(S.c4(1), 1, False) > min_bytes(S.c4(1), 2, False) > 64 * 1024
+    assert min_bytes(S.c4(1), 4, True) <= 64 * 1024
+    assert 56 * 1024 < min_bytes(S.c2(1), 1, False) <= 64 * 1024 < min_bytes(S.c5(1), 1, False)
 
 
 def test_env_counts_leave_partial_workgroups():
