@@ -241,7 +241,14 @@ int zs_observe(zs_handle* h, const uint8_t* env_mask_dev, void* obs_dev, void* s
  *   listed_dev       uint8 [N][num_agents]: agent was in env.agents before the
  *                    step (multi surface: the keys of the returned dicts)
  *   reset_dev        uint8 [N]: 1 when this call reset the env (autoreset)
- * Any output pointer except obs/rewards/done/trunc may be NULL. */
+ * Any output pointer except obs/rewards/done/trunc may be NULL.
+ * zs_step does not report a reset that fails for want of player spawn cells (the implicit first reset, an
+ * autoreset): it returns ZS_OK, reports the env as reset, and leaves it as the failing
+ * Game.__initialize_world__ left it (the players that fit placed, no zombies, the stream after the draws made).
+ * ZS_ENOSPACE then stays in the handle's error word, which zs_step never reads; zs_reset, zs_set_state and the
+ * zs_host_* calls clear the word before they use it, so none of them reports that stale error.  A caller that
+ * must see the failure calls zs_reset (or zs_host_reset / zs_host_step, whose record carries the error of
+ * their own reset work). */
 int zs_step(zs_handle* h, const int32_t* actions_dev, void* obs_dev, double* rewards_dev,
             uint8_t* done_dev, uint8_t* trunc_dev, uint8_t* listed_dev, uint8_t* reset_dev,
             void* stream);

@@ -162,8 +162,9 @@ __global__ void k_get_state(Dev d, int e, int32_t* buf) { state_record(d, e, buf
 // ---------------------------------------------------------------------------
 // the process-global `random` state moved in (rings[e]: the getstate() block and its successor, st[e])
 // (host memory read in place: one round of 16-B loads, 1 248 words = 312 per env)
-__global__ void k_host_unpack(Dev d, const uint32_t* rings, const uint32_t* st) {
+__global__ void k_host_unpack(Dev d, const uint32_t* rings, const uint32_t* st, int* err) {
     const int e = blockIdx.x, t = threadIdx.x;
+    if (e == 0 && t == 0) *err = 0;  // the call's error word starts clear (host_call; no memset launch)
     static_assert(ZS_RING_WORDS % 4 == 0, "16-B copies");
     const uint4* src = (const uint4*)(rings + (size_t)e * ZS_RING_WORDS);
     uint4* dst = (uint4*)(d.ring + (size_t)e * ZS_RING_WORDS);
@@ -188,8 +189,9 @@ __global__ void k_host_pack(Dev d, HostLayout L, const uint8_t* obs, const doubl
     const uint32_t st = d.rngst[e];
     if (tid == 0) {
         r[ZS_HOST_FLAGS] = (done[e] ? 1 : 0) | (trunc[e] ? 2 : 0) | (rst && rst[e] ? 4 : 0);
+        // every env's record carries the call's error word; host_call clears it ahead of the call's launches
+        // (not here: a block that cleared it would hide it from the blocks that read after it)
         r[ZS_HOST_ERR] = *err;
-        *err = 0;  // the next call's error word starts clear (no memset launch)
         r[ZS_HOST_ALOG_N] = d.alog ? d.alog_n[e] : 0;
         r[ZS_HOST_DLOG_N] = d.dlog ? d.dlog_n[e] : 0;
         r[ZS_HOST_RNG + ZS_MT_N] = (int32_t)(st & 1023u);
@@ -1446,11 +1448,17 @@ static int host_call(zs_handle* h, int op, const int32_t* actions_host, const ui
     if (rng_host && (rc = host_stage_rng(h, rng_host))) return rc;
     if (rng_host) {
         const uint32_t* rings = (const uint32_t*)h->d_hin + N * d.A * 3;
-        hipLaunchKernelGGL(k_host_unpack, dim3((unsigned)N), dim3(256), 0, s, h->d, rings, rings + N * ZS_RING_WORDS);
+        hipLaunchKernelGGL(k_host_unpack, dim3((unsigned)N), dim3(256), 0, s, h->d, rings, rings + N * ZS_RING_WORDS,
+                           h->d_err);
         HIPCHK(hipGetLastError());
     }
     uint8_t *done = h->d_hflags, *trunc = done + N, *rst = trunc + N, *listed = rst + N;
-    if (op == HOST_STEP) {  // (d_err is clear: k_host_pack clears it, and zs_reset / zs_set_state before use)
+    // the record's error word is this call's alone: an earlier zs_step whose reset work failed leaves the word
+    // set (zs_step never reads it), and so does an earlier host call (k_host_pack only reads it).  Cleared
+    // ahead of the call's launches without a launch of its own where one is queued anyway: by k_host_unpack
+    // (the drop-ins pass their stream on every call) or by queue_reset; else by a memset
+    if (!rng_host && op != HOST_RESET) HIPCHK(hipMemsetAsync(h->d_err, 0, sizeof(int), s));
+    if (op == HOST_STEP) {
         rc = zs_step(h, h->d_hin, h->d_hobs, h->d_hrew, done, trunc, listed, rst, s);
     } else if (op == HOST_RESET) {
         HIPCHK(hipMemsetAsync(h->d_hflags, 0, N * 3, s));

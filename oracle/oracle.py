@@ -43,6 +43,11 @@ def load(path):
     L.zo_state.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     L.zo_rng_draws.restype = C.c_uint64
     L.zo_rng_draws.argtypes = [C.c_void_p]
+    L.zo_set_rng.argtypes = [C.c_void_p, C.c_void_p]
+    L.zo_rng_words.restype = None
+    L.zo_rng_words.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    L.zo_get_rng.restype = None
+    L.zo_get_rng.argtypes = [C.c_void_p, C.c_void_p]
     L.zo_poke_life.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
     L.zo_poke_obstacle.argtypes = [C.c_void_p, C.c_int, C.c_int]
     L.zo_poke_dead.argtypes = [C.c_void_p, C.c_int, C.c_int]
@@ -150,6 +155,29 @@ class OracleEnv(object):
     def rng_draws(self):
         return int(self.L.zo_rng_draws(self.h))
 
+    def set_rng(self, state):
+        """random.setstate(): `state` is 625 words, the raw 624-word block and the index of its next word."""
+        buf = np.ascontiguousarray(np.asarray(state, dtype=np.uint32).reshape(625))
+        if self.L.zo_set_rng(self.h, buf.ctypes.data):
+            raise ValueError("MT index out of range (0..624)")
+
+    def get_rng(self):
+        """random.getstate()[1] as 625 uint32 words."""
+        buf = np.zeros(625, dtype=np.uint32)
+        self.L.zo_get_rng(self.h, buf.ctypes.data)
+        return buf
+
+    def rng_words(self, n):
+        """The env's next n stream words, consumed (n x random.getrandbits(32))."""
+        buf = np.zeros(n, dtype=np.uint32)
+        self.L.zo_rng_words(self.h, buf.ctypes.data, n)
+        return [int(v) for v in buf]
+
+    def reset_rc(self):
+        """zo_reset's return code (ZS_ENOSPACE when the players do not fit); the env is left as the failing
+        Game.__initialize_world__ left it."""
+        return int(self.L.zo_reset(self.h))
+
     def poke_life(self, which, i, life):
         return self.L.zo_poke_life(self.h, which, i, life)
 
@@ -193,7 +221,8 @@ CENSUS = ("enter_vacated", "same_dest", "target_moved", "target_later", "multi_h
           "obst_int16", "lists", "lists_serial", "chunks", "max_in_chunk", "chunks_all6")
 CENSUS_CASES = CENSUS[:8]
 # ... and the further counters of zo_census_ext / zo_run_hashes_census_ext, which take the buffer's length
-CENSUS_EXT = CENSUS + ("lists_1chunk", "lists_2chunk", "serial_long", "serial_drew", "respawns")
+CENSUS_EXT = CENSUS + ("lists_1chunk", "lists_2chunk", "serial_long", "serial_drew", "respawns", "spawn_empty",
+                       "spawn_one", "spawn_exact", "spawn_plus1", "spawn_short", "zombies_dropped", "player_fails")
 
 
 def run_hashes(builder, seed0, n_envs, steps, n_discrete, threads=0, reset_twice_mod=0, chunk_g=0):
