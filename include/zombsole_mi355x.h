@@ -117,6 +117,13 @@ extern "C" {
                               * the actions it executed, in execution order (zs_action_log; the drop-in
                               * views' World.events) */
 
+#define ZS_FLAG_VIEWER 8u    /* a viewer handle: it holds other handles' envs for encoding (zs_obs_state_unpack,
+                              * zs_observe).  zs_create allocates it like any other handle.  zs_seed, zs_reset,
+                              * zs_step*, zs_gen_actions, zs_set_state, zs_set_rng and the zs_host_* calls
+                              * return ZS_ESTATE on it before any launch; zs_observe, zs_obs_shape, zs_describe,
+                              * zs_state_size, zs_get_state, zs_overflow, zs_destroy and the zs_obs_state_*
+                              * calls work on it */
+
 /* ---- range flags (zs_overflow) -------------------------------------------
  * The reference's obstacle life is an unbounded Python int that carries over resets
  * (game.py:151-155) and keeps falling each time a destroyed Box/Wall is hit again before
@@ -297,6 +304,33 @@ int zs_set_rng(zs_handle* h, int32_t env, const uint32_t* state_host, void* stre
  * envs since zs_create or the last call with clear != 0.  Lossless results need
  * !(flags & ZS_OVF_INT32), and !(flags & ZS_OVF_INT16) for ZS_DTYPE_I16 observations. */
 int zs_overflow(zs_handle* h, uint32_t* flags_host, int32_t clear, void* stream);
+
+/* ---- observation-state records ------------------------------------------------------------------
+ * An env's observation is a function of nine of its arrays alone: things' positions, lives, weapons and
+ * presence, the dead-body bitmap, obstacle presence and life, and the two words that say which chunks of
+ * the bitmap and of the lives may differ from a fresh env's.  A record is those arrays of one env in one
+ * block of rec_bytes bytes (a multiple of 16), a small fraction of the observations they encode, so a
+ * centralised learner can exchange records instead of observations (vector.StepGather(mode="state")):
+ * every handle packs its envs, a viewer handle (ZS_FLAG_VIEWER) unpacks all of them and zs_observe on it
+ * re-encodes them, bit-identical to the observations the source handles wrote.
+ *
+ * zs_obs_state_layout: out[0] = rec_bytes; out[1..9] = byte offsets of the sections hp_dirty (u32),
+ * dead_dirty (u32), pos (i32 [E], x | y << 16), life (i32 [E]), dead (u32 [ceil(W*H/32)]), obst_present
+ * (u32 [ceil(O/32)]), obst_hp ([O]), weapon (u8 [E]), present (u8 [E]); out[10] = offset of the zero
+ * padding that ends the record; out[11] = bytes of an obst_hp element: 4 (int32), or 2 for ZS_DTYPE_I16
+ * handles with the channels encoding (int16, the life saturated at -32768 as those observations saturate
+ * it themselves).
+ * zs_obs_state_pack: the records of all N envs into rec_dev, [N][rec_bytes], 16-byte aligned; every byte
+ * of every record is written (padding: zeros).  Any handle.
+ * zs_obs_state_unpack: records [0, n) of rec_dev into envs [env0, env0 + n) of a viewer handle (any other
+ * handle: ZS_ESTATE); its other envs are untouched.  rec_bytes must equal the handle's own and the range
+ * lie inside [0, N), else ZS_EINVAL with nothing launched.  The packing and the unpacking handle must share
+ * the map and the entity counts (agents, bots, zombie slots), the observation dtype and encoding: nothing in
+ * a record says which handle wrote it, and its contents are not validated.  The source's ZS_OVF_* flags do
+ * not travel: read zs_overflow on the source handles. */
+int zs_obs_state_layout(const zs_handle* h, int32_t out[12]);
+int zs_obs_state_pack(zs_handle* h, void* rec_dev, void* stream);
+int zs_obs_state_unpack(zs_handle* h, const void* rec_dev, int32_t rec_bytes, int32_t env0, int32_t n, void* stream);
 
 /* Diagnostics (not part of the reference surface): when enabled, every k_tick
  * (the step kernel), k_obs (the observation kernel) and k_reset (world rebuild)

@@ -29,6 +29,7 @@ DTYPE_I32, DTYPE_I64, DTYPE_I16 = 0, 1, 2
 FLAG_AUTORESET = 1
 FLAG_DEBUG = 2
 FLAG_DEATH_LOG = 4  # zs_death_log: the drop-in views' decoration order and removed zombies' final values
+FLAG_VIEWER = 8  # a handle that holds other handles' envs for encoding (zs_obs_state_unpack + zs_observe)
 OVF_INT16, OVF_INT32 = 1, 2  # zs_overflow range flags
 STATE_HEADER, STATE_ENTITY_WORDS = 16, 8
 
@@ -49,6 +50,30 @@ class zs_map_desc(C.Structure):
                 ("n_objectives", C.c_int32), ("objective_xy", C.POINTER(C.c_int32)),
                 ("n_player_spawns", C.c_int32), ("player_spawn_xy", C.POINTER(C.c_int32)),
                 ("n_zombie_spawns", C.c_int32), ("zombie_spawn_xy", C.POINTER(C.c_int32))]
+
+
+OBS_STATE_SECTIONS = ("hp_dirty", "dead_dirty", "pos", "life", "dead", "obst_present", "obst_hp", "weapon", "present")
+
+
+def obs_state_layout(E, O, DW, OW, obs_dtype):
+    """Mirror of obs_state_layout() (csrc/zs_obs_state.hpp): the byte offset of every section of an env's
+    observation-state record, "pad" (where the zero padding starts), "rec_bytes" (a multiple of 16) and
+    "hp_bytes" (2 for DTYPE_I16: the obstacle HP as int16 saturated at -32768, else 4)."""
+    hp = 2 if obs_dtype == DTYPE_I16 else 4
+    L, o = {}, 0
+    for name, nbytes in zip(OBS_STATE_SECTIONS, (4, 4, 4 * E, 4 * E, 4 * DW, 4 * OW, hp * O, E, E)):
+        L[name] = o
+        o += nbytes
+    L["pad"] = o
+    L["rec_bytes"] = (o + 15) // 16 * 16
+    L["hp_bytes"] = hp
+    return L
+
+
+def obs_state_record_dtype(obs_dtype, obs_encoding):
+    """Mirror of obs_state_record_dtype(): an int16 handle with the simple encoding ships int32 HP (that encoding
+    folds the unsaturated life into its code)."""
+    return DTYPE_I32 if obs_dtype == DTYPE_I16 and obs_encoding != ENC_CHANNELS else obs_dtype
 
 
 LAUNCH_FIELDS = ["fused", "fobs", "tick_waves", "lds_budget", "rw_need", "reset_wgs", "reset_stream", "reset_lists",
@@ -152,7 +177,7 @@ class ConfigBuilder(object):
 
     def __init__(self, num_envs, map_, rules, agent_weapons, agent_codes, bot_types, initial_zombies,
                  minimum_zombies, reward_mode, obs_scope, obs_encoding, obs_width, obs_dtype,
-                 max_episode_steps=0, autoreset=True, lanes_per_env=0, debug=False):
+                 max_episode_steps=0, autoreset=True, lanes_per_env=0, debug=False, viewer=False):
         m = map_ if isinstance(map_, Map) else load_map(map_)
         self.map = m
 
@@ -177,7 +202,8 @@ class ConfigBuilder(object):
                              len(self._bt), p32(self._bt), int(initial_zombies), int(minimum_zombies),
                              int(reward_mode), int(obs_scope), int(obs_encoding), int(obs_width),
                              int(obs_dtype), int(max_episode_steps),
-                             (FLAG_AUTORESET if autoreset else 0) | (FLAG_DEBUG if debug else 0),
+                             (FLAG_AUTORESET if autoreset else 0) | (FLAG_DEBUG if debug else 0) |
+                             (FLAG_VIEWER if viewer else 0),
                              int(lanes_per_env))
         self._launch = None
 
@@ -201,6 +227,23 @@ class ConfigBuilder(object):
         if self._launch is None:
             return {}
         return {f: getattr(self._launch, f) for f in LAUNCH_FIELDS if getattr(self._launch, f)}
+
+    def viewer(self, num_envs):
+        """The config of a viewer handle (FLAG_VIEWER) for num_envs envs of this config's map, entities and
+        observations (it shares this builder's arrays)."""
+        import copy
+        b = copy.copy(self)
+        b.cfg = zs_config.from_buffer_copy(self.cfg)
+        b.cfg.num_envs = int(num_envs)
+        b.cfg.flags |= FLAG_VIEWER
+        return b
+
+    def obs_state_layout(self):
+        """The observation-state record of this config's handles (zs_obs_state_layout without a device)."""
+        c, m = self.cfg, self.cfg.map
+        E = c.num_agents + c.num_bots + max(c.initial_zombies, c.minimum_zombies)
+        return obs_state_layout(E, m.n_obstacles, (m.width * m.height + 31) // 32, (m.n_obstacles + 31) // 32,
+                                obs_state_record_dtype(c.obs_dtype, c.obs_encoding))
 
     @property
     def num_agents(self):
@@ -228,7 +271,7 @@ class ConfigBuilder(object):
 def single_env_config(num_envs, rules_name, player_names, map_name, agent_id, initial_zombies=0,
                       minimum_zombies=0, observation_scope="world", observation_position_encoding="simple",
                       agent_weapon="rifle", max_episode_steps=0, obs_dtype=DTYPE_I32, autoreset=True,
-                      lanes_per_env=0, debug=False):
+                      lanes_per_env=0, debug=False, viewer=False):
     """zs_config for the ZombsoleGymEnv surface (gym_env.py:49-83): one agent + bots."""
     m = load_map(map_name)
     rules = rules_id(rules_name)
@@ -238,13 +281,14 @@ def single_env_config(num_envs, rules_name, player_names, map_name, agent_id, in
     enc = parse_encoding(observation_position_encoding)
     return ConfigBuilder(num_envs, m, rules, weapons, [agent_code(agent_id)], bots, initial_zombies,
                          minimum_zombies, REWARD_SINGLE, scope, enc, width, obs_dtype, max_episode_steps,
-                         autoreset, lanes_per_env, debug)
+                         autoreset, lanes_per_env, debug, viewer)
 
 
 def multi_env_config(num_envs, rules_name, player_names, map_name, agent_ids, initial_zombies=0,
                      minimum_zombies=0, observation_surroundings_width=21,
                      observation_position_encoding_style="channels", agent_weapons="rifle",
-                     max_episode_steps=0, obs_dtype=DTYPE_I64, autoreset=True, lanes_per_env=0, debug=False):
+                     max_episode_steps=0, obs_dtype=DTYPE_I64, autoreset=True, lanes_per_env=0, debug=False,
+                     viewer=False):
     """zs_config for the MultiagentZombsoleEnv surface (gym/multiagent_env.py:25-78)."""
     w = int(observation_surroundings_width)
     if (w % 2 == 0) or (w <= 1):
@@ -258,4 +302,4 @@ def multi_env_config(num_envs, rules_name, player_names, map_name, agent_ids, in
     weapons = [weapon_id(n) for n in names]
     return ConfigBuilder(num_envs, m, rules, weapons, [agent_code(a) for a in ids], bots, initial_zombies,
                          minimum_zombies, REWARD_MULTI, OBS_SURROUNDINGS, enc, w, obs_dtype,
-                         max_episode_steps, autoreset, lanes_per_env, debug)
+                         max_episode_steps, autoreset, lanes_per_env, debug, viewer)

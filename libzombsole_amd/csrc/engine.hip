@@ -6,7 +6,8 @@
 // respawns, one wave per env) and the observation kernel (zs_obs.hpp: k_obs_ring / k_obs_pipe
 // persistent store streams, k_obs_gather for large maps, k_obs in general).  zs_step_graph replays
 // a step as a hipGraph.  k_seed / k_gen_actions / k_get_state / k_set_state are the small helpers
-// behind the ABI.
+// behind the ABI; k_obs_state_pack / k_obs_state_unpack move the observation encoders' inputs between
+// handles as per-env records (zs_obs_state.hpp).
 //
 // Semantics follow the reference exactly (parity: tests/); every sqrt range
 // test of the reference is replaced by its exact integer d^2 equivalent.
@@ -23,6 +24,7 @@
 #include "zs_launch.hpp"
 #include "zs_reset.hpp"
 #include "zs_obs.hpp"
+#include "zs_obs_state.hpp"
 
 // ---------------------------------------------------------------------------
 // seeding: random.seed(int) (init_by_array over abs(n) in 32-bit little-endian words)
@@ -262,6 +264,136 @@ __global__ void k_set_state(Dev d, int e, const int32_t* buf, int* err) {
     d.dead_dirty[e] = 0xffffffffu;
 }
 
+// ---------------------------------------------------------------------------
+// observation-state records (zs_obs_state.hpp): k_obs_state_pack copies the nine per-env arrays the
+// observation encoders read into one record per env, k_obs_state_unpack copies records into a viewer's envs.
+// Both walk a record in 16-B chunks, `wpe` waves of a 256-thread workgroup per env (1: four envs per
+// workgroup, 4: one), grid-stride over envs.  The record side is 16-B aligned (one 16-B store / load per
+// chunk).  The engine side is not: a [N][E] int32 row starts at byte 4 e E and a section at any 4-B offset
+// of the record, so a chunk inside one 4-byte section moves as 16 B when its engine address allows and as
+// four dwords otherwise; eight int16 HP elements of a record chunk are 32 B of the env's int32 row (two 16-B
+// accesses when aligned, else eight dwords); the u8 rows and a chunk that straddles sections move by element.
+// ---------------------------------------------------------------------------
+// the engine-side word of the record's dword at byte b (b % 4 == 0, b inside the 4-byte sections); *sec: its section
+__device__ __forceinline__ uint32_t* os_word(const Dev& d, const ObsStateLayout& L, size_t e, int b, int* sec) {
+    if (b >= L.obst_hp) return *sec = 6, (uint32_t*)d.obst_hp + e * d.O + ((b - L.obst_hp) >> 2);
+    if (b >= L.obst_present) return *sec = 5, d.obst_present + e * d.OW + ((b - L.obst_present) >> 2);
+    if (b >= L.dead) return *sec = 4, d.dead + e * d.DW + ((b - L.dead) >> 2);
+    if (b >= L.life) return *sec = 3, (uint32_t*)d.life + e * d.E + ((b - L.life) >> 2);
+    if (b >= L.pos) return *sec = 2, (uint32_t*)d.pos + e * d.E + ((b - L.pos) >> 2);
+    if (b >= L.dead_dirty) return *sec = 1, d.dead_dirty + e;
+    return *sec = 0, d.hp_dirty + e;
+}
+
+// the record's two bytes at p (p % 2 == 0) past the 4-byte sections: an int16 HP element, u8 rows, padding
+__device__ __forceinline__ uint32_t os_tail_get(const Dev& d, const ObsStateLayout& L, size_t e, int p) {
+    if (p < L.weapon) return (uint16_t)(int16_t)max(-32768, min(d.obst_hp[e * d.O + ((p - L.obst_hp) >> 1)], 32767));
+    uint32_t v = 0;
+    for (int k = 0; k < 2; k++) {
+        const int q = p + k;
+        const uint32_t by = q < L.present ? d.weapon[e * d.E + (q - L.weapon)] : q < L.pad ? d.present[e * d.E + (q - L.present)] : 0u;
+        v |= by << (8 * k);
+    }
+    return v;
+}
+__device__ __forceinline__ void os_tail_put(const Dev& d, const ObsStateLayout& L, size_t e, int p, uint32_t v) {
+    if (p < L.weapon) {
+        d.obst_hp[e * d.O + ((p - L.obst_hp) >> 1)] = (int32_t)(int16_t)(v & 0xffffu);
+        return;
+    }
+    for (int k = 0; k < 2; k++) {
+        const int q = p + k;
+        const uint8_t by = (uint8_t)(v >> (8 * k));
+        if (q < L.present) d.weapon[e * d.E + (q - L.weapon)] = by;
+        else if (q < L.pad) d.present[e * d.E + (q - L.present)] = by;
+    }
+}
+
+// rec [n][L.rec_bytes]: record r is env env0 + r of the handle; PACK: engine -> record, else record -> engine
+template <bool PACK>
+__device__ __forceinline__ void obs_state_copy(const Dev& d, const ObsStateLayout& L, int wpe, int env0, int n, uint4* rec) {
+    const int team = wpe * 64, per_wg = 256 / team;
+    const int t = threadIdx.x % team;
+    const int nch = L.rec_bytes >> 4;
+    const int words_end = L.hp_bytes == 4 ? L.weapon : L.obst_hp;  // end of the 4-byte sections
+    for (int r = blockIdx.x * per_wg + threadIdx.x / team; r < n; r += gridDim.x * per_wg) {
+        const size_t e = (size_t)(env0 + r);
+        uint4* row = rec + (size_t)r * nch;
+        for (int c = t; c < nch; c += team) {
+            const int b0 = c << 4;
+            uint32_t w[4];
+            if (!PACK) {
+                const uint4 v = row[c];
+                w[0] = v.x, w[1] = v.y, w[2] = v.z, w[3] = v.w;
+            }
+            if (b0 + 16 <= words_end) {
+                int s0, s3;
+                uint32_t* p0 = os_word(d, L, e, b0, &s0);
+                (void)os_word(d, L, e, b0 + 12, &s3);
+                if (s0 == s3 && ((uintptr_t)p0 & 15) == 0) {  // one section, 16-B aligned on the engine side
+                    if (PACK) row[c] = *(const uint4*)p0;
+                    else *(uint4*)p0 = uint4{w[0], w[1], w[2], w[3]};
+                    continue;
+                }
+            }
+            if (L.hp_bytes == 2 && b0 >= L.obst_hp && b0 + 16 <= L.weapon) {
+                // eight int16 HP elements of the record = 32 B of the env's int32 row, all loads issued first
+                int32_t* p = d.obst_hp + e * d.O + ((b0 - L.obst_hp) >> 1);
+                const bool al = ((uintptr_t)p & 15) == 0;
+                int v[8];
+                if (PACK) {
+                    if (al) {
+                        const int4 lo = ((const int4*)p)[0], hi = ((const int4*)p)[1];
+                        v[0] = lo.x, v[1] = lo.y, v[2] = lo.z, v[3] = lo.w, v[4] = hi.x, v[5] = hi.y, v[6] = hi.z, v[7] = hi.w;
+                    } else {
+#pragma unroll
+                        for (int k = 0; k < 8; k++) v[k] = p[k];
+                    }
+#pragma unroll
+                    for (int j = 0; j < 4; j++)
+                        w[j] = (uint32_t)(uint16_t)(int16_t)max(-32768, min(v[2 * j], 32767)) |
+                               ((uint32_t)(uint16_t)(int16_t)max(-32768, min(v[2 * j + 1], 32767)) << 16);
+                    row[c] = uint4{w[0], w[1], w[2], w[3]};
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 4; j++) v[2 * j] = (int16_t)(w[j] & 0xffffu), v[2 * j + 1] = (int16_t)(w[j] >> 16);
+                    if (al) {
+                        ((int4*)p)[0] = int4{v[0], v[1], v[2], v[3]};
+                        ((int4*)p)[1] = int4{v[4], v[5], v[6], v[7]};
+                    } else {
+#pragma unroll
+                        for (int k = 0; k < 8; k++) p[k] = v[k];
+                    }
+                }
+                continue;
+            }
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const int b = b0 + 4 * j;
+                if (b < words_end) {
+                    int s;
+                    uint32_t* p = os_word(d, L, e, b, &s);
+                    if (PACK) w[j] = *p;
+                    else *p = w[j];
+                } else if (PACK) {
+                    w[j] = os_tail_get(d, L, e, b) | (os_tail_get(d, L, e, b + 2) << 16);
+                } else {
+                    os_tail_put(d, L, e, b, w[j]);
+                    os_tail_put(d, L, e, b + 2, w[j] >> 16);
+                }
+            }
+            if (PACK) row[c] = uint4{w[0], w[1], w[2], w[3]};
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_obs_state_pack(Dev d, ObsStateLayout L, int wpe, int n, uint4* rec) {
+    obs_state_copy<true>(d, L, wpe, 0, n, rec);
+}
+__global__ __launch_bounds__(256) void k_obs_state_unpack(Dev d, ObsStateLayout L, int wpe, int env0, int n, const uint4* rec) {
+    obs_state_copy<false>(d, L, wpe, env0, n, (uint4*)rec);
+}
+
 __global__ void k_init_pending(Dev d, int* list, int* count) {
     int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e == 0) {
@@ -370,6 +502,17 @@ static hipEvent_t prof_event(zs_handle* h, int* idx) {
 
 extern "C" const char* zs_last_error(void) { return g_err.c_str(); }
 
+// a viewer handle (ZS_FLAG_VIEWER) holds other handles' envs for encoding: nothing steps, seeds or resets it
+static int viewer_refused(const zs_handle* h, const char* call) {
+    if (!(h->cfg.flags & ZS_FLAG_VIEWER)) return ZS_OK;
+    return fail(ZS_ESTATE, std::string(call) + ": not on a viewer handle (ZS_FLAG_VIEWER)");
+}
+#define NOT_ON_VIEWER(h, call)                  \
+    do {                                        \
+        int _v = viewer_refused((h), (call));   \
+        if (_v) return _v;                      \
+    } while (0)
+
 template <typename T>
 static int dalloc(zs_handle* h, T** p, size_t count) {
     size_t bytes = std::max<size_t>(count * sizeof(T), 16);
@@ -462,6 +605,8 @@ static int validate(const zs_config* c) {
         if (c->bot_types[p] < ZS_BOT_TERMINATOR || c->bot_types[p] > ZS_BOT_RANDOMAN) return fail(ZS_EINVAL, "bad bot type");
     return ZS_OK;
 }
+
+static int seed_envs(zs_handle* h, int32_t env0, int32_t n, const uint64_t* seeds_host, void* stream);
 
 // zs_create's handle until it succeeds: an early return frees it with everything allocated so far
 struct HandleOwner {
@@ -790,7 +935,7 @@ extern "C" int zs_create(const zs_config* cfg, int device, zs_handle** out) {
     // default seeds: env index (every env has a valid stream even if never seeded)
     std::vector<uint64_t> seeds(N);
     for (size_t i = 0; i < N; i++) seeds[i] = i;
-    TRY(zs_seed(h, 0, (int)N, seeds.data(), nullptr));
+    TRY(seed_envs(h, 0, (int)N, seeds.data(), nullptr));
     hipError_t se = hipDeviceSynchronize();
     if (se != hipSuccess) return fail(ZS_EHIP, std::string("zs_create sync: ") + hipGetErrorString(se));
     *out = h;
@@ -812,6 +957,11 @@ extern "C" int zs_obs_shape(const zs_handle* h, int32_t out[4]) {
 
 extern "C" int zs_seed(zs_handle* h, int32_t env0, int32_t n, const uint64_t* seeds_host, void* stream) {
     if (!h || !seeds_host) return fail(ZS_EINVAL, "null argument");
+    NOT_ON_VIEWER(h, "zs_seed");
+    return seed_envs(h, env0, n, seeds_host, stream);
+}
+
+static int seed_envs(zs_handle* h, int32_t env0, int32_t n, const uint64_t* seeds_host, void* stream) {
     if (env0 < 0 || n < 0 || env0 + n > h->d.N) return fail(ZS_EINVAL, "env range out of bounds");
     if (n == 0) return ZS_OK;
     hipStream_t s = (hipStream_t)stream;
@@ -943,6 +1093,7 @@ static int queue_reset(zs_handle* h, const uint8_t* env_mask_dev, void* obs_dev,
 
 extern "C" int zs_reset(zs_handle* h, const uint8_t* env_mask_dev, void* obs_dev, void* stream) {
     if (!h) return fail(ZS_EINVAL, "null handle");
+    NOT_ON_VIEWER(h, "zs_reset");
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(hipSetDevice(h->device));
     int rc = queue_reset(h, env_mask_dev, obs_dev, s);
@@ -968,6 +1119,7 @@ extern "C" int zs_observe(zs_handle* h, const uint8_t* env_mask_dev, void* obs_d
 extern "C" int zs_step(zs_handle* h, const int32_t* actions_dev, void* obs_dev, double* rewards_dev, uint8_t* done_dev,
                        uint8_t* trunc_dev, uint8_t* listed_dev, uint8_t* reset_dev, void* stream) {
     if (!h || !actions_dev || !rewards_dev || !done_dev || !trunc_dev) return fail(ZS_EINVAL, "null argument");
+    NOT_ON_VIEWER(h, "zs_step");
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(hipSetDevice(h->device));
     // 1) rebuild the envs that ended at the previous call (list[p]); fused into the tick launch
@@ -1057,6 +1209,7 @@ extern "C" int zs_step(zs_handle* h, const int32_t* actions_dev, void* obs_dev, 
 
 extern "C" int zs_gen_actions(zs_handle* h, uint64_t step, int32_t n_discrete, int32_t* actions_dev, void* stream) {
     if (!h || !actions_dev) return fail(ZS_EINVAL, "null argument");
+    NOT_ON_VIEWER(h, "zs_gen_actions");
     if (n_discrete < 1 || n_discrete > 7) return fail(ZS_EINVAL, "n_discrete must be in 1..7");
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(hipSetDevice(h->device));
@@ -1081,6 +1234,7 @@ extern "C" int zs_step_graph_n(zs_handle* h, uint64_t step0, int32_t n_discrete,
                                void* obs_dev, double* rewards_dev, uint8_t* done_dev, uint8_t* trunc_dev,
                                uint8_t* listed_dev, uint8_t* reset_dev, void* stream) {
     if (!h || !actions_dev || !rewards_dev || !done_dev || !trunc_dev) return fail(ZS_EINVAL, "null argument");
+    NOT_ON_VIEWER(h, "zs_step_graph");
     // n_discrete = 0: the caller's actions (no policy launch; the graph replays zs_step on actions_dev)
     if (n_discrete < 0 || n_discrete > 7) return fail(ZS_EINVAL, "n_discrete must be in 0..7");
     if (n_steps < 1 || n_steps > 64) return fail(ZS_EINVAL, "n_steps must be in 1..64");
@@ -1177,6 +1331,7 @@ extern "C" int zs_get_state(zs_handle* h, int32_t env, int32_t* buf_host, void* 
 
 extern "C" int zs_set_state(zs_handle* h, int32_t env, const int32_t* buf_host, void* stream) {
     if (!h || !buf_host) return fail(ZS_EINVAL, "null argument");
+    NOT_ON_VIEWER(h, "zs_set_state");
     if (env < 0 || env >= h->d.N) return fail(ZS_EINVAL, "env index out of range");
     {  // a present thing stands on a map cell (the occupancy and observation kernels index the map by it)
         const int32_t* r = buf_host + ZS_STATE_HEADER;
@@ -1216,6 +1371,63 @@ extern "C" int zs_overflow(zs_handle* h, uint32_t* flags_host, int32_t clear, vo
 }
 
 // ---------------------------------------------------------------------------
+// observation-state records (zs_obs_state.hpp; kernels above)
+// ---------------------------------------------------------------------------
+static ObsStateLayout handle_obs_state_layout(const zs_handle* h) {
+    const Dev& d = h->d;
+    return obs_state_layout(d.E, d.O, d.DW, d.OW, obs_state_record_dtype(d.obs_dtype, d.obs_enc));
+}
+
+// waves of a workgroup per env (one wave walks up to four 16-B chunks per lane) and the launch's workgroups
+static void obs_state_geometry(const ObsStateLayout& L, int n, int* wpe, unsigned* grid) {
+    *wpe = L.rec_bytes > 4 * 64 * 16 ? 4 : 1;
+    const int per_wg = 4 / *wpe;
+    *grid = (unsigned)std::min((n + per_wg - 1) / per_wg, 256 * 16);  // grid-stride past 16 workgroups per CU
+}
+
+extern "C" int zs_obs_state_layout(const zs_handle* h, int32_t out[12]) {
+    if (!h || !out) return fail(ZS_EINVAL, "null argument");
+    const ObsStateLayout L = handle_obs_state_layout(h);
+    const int32_t v[12] = {L.rec_bytes, L.hp_dirty, L.dead_dirty, L.pos,     L.life, L.dead,
+                           L.obst_present, L.obst_hp, L.weapon,     L.present, L.pad,  L.hp_bytes};
+    std::memcpy(out, v, sizeof(v));
+    return ZS_OK;
+}
+
+extern "C" int zs_obs_state_pack(zs_handle* h, void* rec_dev, void* stream) {
+    if (!h || !rec_dev) return fail(ZS_EINVAL, "null argument");
+    if ((uintptr_t)rec_dev & 15) return fail(ZS_EINVAL, "rec_dev must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(hipSetDevice(h->device));
+    const ObsStateLayout L = handle_obs_state_layout(h);
+    int wpe;
+    unsigned grid;
+    obs_state_geometry(L, h->d.N, &wpe, &grid);
+    hipLaunchKernelGGL(k_obs_state_pack, dim3(grid), dim3(256), 0, s, h->d, L, wpe, h->d.N, (uint4*)rec_dev);
+    HIPCHK(hipGetLastError());
+    return ZS_OK;
+}
+
+extern "C" int zs_obs_state_unpack(zs_handle* h, const void* rec_dev, int32_t rec_bytes, int32_t env0, int32_t n,
+                                   void* stream) {
+    if (!h || !rec_dev) return fail(ZS_EINVAL, "null argument");
+    if (!(h->cfg.flags & ZS_FLAG_VIEWER)) return fail(ZS_ESTATE, "zs_obs_state_unpack: viewer handles only (ZS_FLAG_VIEWER)");
+    const ObsStateLayout L = handle_obs_state_layout(h);
+    if (rec_bytes != L.rec_bytes) return fail(ZS_EINVAL, "rec_bytes differs from the handle's (zs_obs_state_layout)");
+    if (env0 < 0 || n < 0 || (int64_t)env0 + n > h->d.N) return fail(ZS_EINVAL, "env range out of bounds");
+    if ((uintptr_t)rec_dev & 15) return fail(ZS_EINVAL, "rec_dev must be 16-byte aligned");
+    if (n == 0) return ZS_OK;
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(hipSetDevice(h->device));
+    int wpe;
+    unsigned grid;
+    obs_state_geometry(L, n, &wpe, &grid);
+    hipLaunchKernelGGL(k_obs_state_unpack, dim3(grid), dim3(256), 0, s, h->d, L, wpe, env0, n, (const uint4*)rec_dev);
+    HIPCHK(hipGetLastError());
+    return ZS_OK;
+}
+
+// ---------------------------------------------------------------------------
 // An env's MT19937 stream in CPython's random.getstate() form: state[0..623] = the raw
 // block being consumed, state[624] = index of the next word (0..624; 624 = exhausted, the
 // next draw twists).  The single-env wrappers move the process-global `random` state in
@@ -1241,6 +1453,7 @@ extern "C" int zs_get_rng(zs_handle* h, int32_t env, uint32_t* state_host, void*
 
 extern "C" int zs_set_rng(zs_handle* h, int32_t env, const uint32_t* state_host, void* stream) {
     if (!h || !state_host) return fail(ZS_EINVAL, "null argument");
+    NOT_ON_VIEWER(h, "zs_set_rng");
     if (env < 0 || env >= h->d.N) return fail(ZS_EINVAL, "env index out of range");
     if (state_host[ZS_MT_N] > ZS_MT_N) return fail(ZS_EINVAL, "MT index out of range (0..624)");
     hipStream_t s = (hipStream_t)stream;
@@ -1438,6 +1651,7 @@ enum { HOST_STEP = 0, HOST_RESET = 1, HOST_OBSERVE = 2 };
 
 static int host_call(zs_handle* h, int op, const int32_t* actions_host, const uint32_t* rng_host, int32_t* rec_host,
                      hipStream_t s) {
+    NOT_ON_VIEWER(h, "zs_host_step / zs_host_reset / zs_host_observe");
     HIPCHK(hipSetDevice(h->device));
     int rc = host_init(h);
     if (rc) return rc;
@@ -1482,6 +1696,7 @@ static int host_call(zs_handle* h, int op, const int32_t* actions_host, const ui
 
 extern "C" int zs_host_layout(zs_handle* h, int32_t out[8]) {
     if (!h || !out) return fail(ZS_EINVAL, "null argument");
+    NOT_ON_VIEWER(h, "zs_host_layout");
     const HostLayout L = host_layout(h);
     const int32_t v[8] = {L.words, L.rew, L.alog, L.dlog, L.state, L.obs, L.obs_bytes, L.R};
     std::memcpy(out, v, sizeof(v));

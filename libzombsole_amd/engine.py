@@ -15,7 +15,8 @@ LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_build", "l
 SYMBOLS = ["zs_last_error", "zs_create", "zs_destroy", "zs_obs_shape", "zs_seed", "zs_reset", "zs_step", "zs_observe",
            "zs_gen_actions", "zs_step_graph", "zs_step_graph_n", "zs_state_size", "zs_get_state", "zs_set_state", "zs_get_rng", "zs_set_rng", "zs_overflow", "zs_profile", "zs_profile_read", "zs_describe",
            "zs_debug_stamps", "zs_debug_stamps_wg", "zs_debug_timeline", "zs_debug_lists", "zs_death_log", "zs_action_log",
-           "zs_host_layout", "zs_host_step", "zs_host_reset", "zs_host_observe"]
+           "zs_host_layout", "zs_host_step", "zs_host_reset", "zs_host_observe",
+           "zs_obs_state_layout", "zs_obs_state_pack", "zs_obs_state_unpack"]
 
 _lib = None
 
@@ -70,6 +71,9 @@ def load_library(path=None):
     L.zs_host_step.argtypes = [vp, vp, vp, vp, vp]
     L.zs_host_reset.argtypes = [vp, vp, vp, vp]
     L.zs_host_observe.argtypes = [vp, vp, vp]
+    L.zs_obs_state_layout.argtypes = [vp, C.POINTER(i32)]
+    L.zs_obs_state_pack.argtypes = [vp, vp, vp]
+    L.zs_obs_state_unpack.argtypes = [vp, vp, i32, i32, i32, vp]
     for s in SYMBOLS:
         if s != "zs_last_error":
             getattr(L, s).restype = C.c_int
@@ -234,12 +238,62 @@ class Engine(object):
         fixed (self.actions, an output set) and rewrites their contents each step."""
         return self.step_graph(0, 0, out=out, actions=actions)
 
-    def observe(self, mask=None):
-        """Re-encode observations from the current state (after pokes)."""
-        rc = self.L.zs_observe(self.h, _ptr(mask), _ptr(self.obs), self._stream())
+    def observe(self, mask=None, out=None):
+        """Re-encode observations from the current state (after pokes, or a viewer's after
+        unpack_obs_state) into `out` (default: self.obs), a tensor of the observations' dtype with at least
+        N rows of obs_shape."""
+        o = self.obs if out is None else out
+        if out is not None:
+            if (o.dtype != self.obs_dtype or o.device != self.device or not o.is_contiguous() or
+                    tuple(o.shape[1:]) != tuple(self.obs_shape) or o.shape[0] < self.N):
+                raise ValueError("observe: out must be a contiguous %s tensor [rows >= %d]%s on %s"
+                                 % (self.obs_dtype, self.N, list(self.obs_shape), self.device))
+        rc = self.L.zs_observe(self.h, _ptr(mask), _ptr(o), self._stream())
         if rc:
             _raise(self.L, rc, "zs_observe")
-        return self.obs
+        return o
+
+    # -- observation-state records (zs_obs_state_*): what the encoders read of an env, a fraction of its observation
+    def obs_state_layout(self):
+        """zs_obs_state_layout as a dict: the byte offset of every section of an env's record (the names of
+        _abi.OBS_STATE_SECTIONS), "pad", "rec_bytes" and "hp_bytes"."""
+        if getattr(self, "_osl", None) is None:
+            out = (C.c_int32 * 12)()
+            rc = self.L.zs_obs_state_layout(self.h, out)
+            if rc:
+                _raise(self.L, rc, "zs_obs_state_layout")
+            names = ("rec_bytes",) + _abi.OBS_STATE_SECTIONS + ("pad", "hp_bytes")
+            self._osl = dict(zip(names, [int(v) for v in out]))
+        return self._osl
+
+    def _check_records(self, rec, what, rows):
+        t = self.torch
+        nb = self.obs_state_layout()["rec_bytes"]
+        if (rec.dtype != t.uint8 or rec.dim() != 2 or rec.shape[1] != nb or not rec.is_contiguous() or
+                rec.device != self.device or rec.shape[0] < rows or rec.data_ptr() % 16):
+            raise ValueError("%s: records are a contiguous, 16-byte aligned uint8 tensor [rows >= %d, %d] on %s"
+                             % (what, rows, nb, self.device))
+
+    def pack_obs_state(self, out=None):
+        """Every env's observation-state record into `out`, uint8 [rows >= N, rec_bytes] (default: a new
+        tensor of N rows); the first N rows are written, every byte of them."""
+        if out is None:
+            out = self.torch.empty((self.N, self.obs_state_layout()["rec_bytes"]), dtype=self.torch.uint8,
+                                   device=self.device)
+        self._check_records(out, "pack_obs_state", self.N)
+        rc = self.L.zs_obs_state_pack(self.h, _ptr(out), self._stream())
+        if rc:
+            _raise(self.L, rc, "zs_obs_state_pack")
+        return out
+
+    def unpack_obs_state(self, rec, env0=0, n=None):
+        """Viewer engines only: records rec[:n] (default: all rows) into envs [env0, env0 + n); observe() then
+        encodes them.  The records come from engines of the same map, entity counts and observation form."""
+        n = rec.shape[0] if n is None else int(n)
+        self._check_records(rec, "unpack_obs_state", n)
+        rc = self.L.zs_obs_state_unpack(self.h, _ptr(rec), int(rec.shape[1]), int(env0), n, self._stream())
+        if rc:
+            _raise(self.L, rc, "zs_obs_state_unpack")
 
     def gen_actions(self, step, n_discrete, out=None):
         o = self.actions if out is None else out

@@ -185,9 +185,20 @@ class StepGather(object):
     ordered on the current stream only (obs(copy=True) returns a copy).  A consumer that reads a step's
     gathered values on the communication stream instead (a learner overlapping with the next step)
     passes after=fn to step(): fn(k) runs there right after the collectives that fill set k.
+
+    mode="state" exchanges observation-state records instead of observations (Engine.pack_obs_state: what the
+    encoders read of an env, 1 584 B against 10 584 B of observations at C5).  After run(out) the rank packs
+    its envs into its slice of g_state[k] (uint8 [world * m, rec_bytes], out.state) on the caller's stream; the
+    communication stream all-gathers g_state[k] and the flat buffer, unpacks all world * m records into
+    `viewer` (an Engine built with viewer=True and world * m envs; default: one built from the engine's
+    config) and re-encodes them into g_obs[k] (viewer.observe) before after(k).  obs(), rewards(), ... and
+    the pending-event protocol mean what they mean in mode="obs", and the values are the same.  The step
+    still writes the rank's own observations (into its slice of g_obs[k], which the viewer then rewrites
+    with the same values).  Padding rows carry zero records; _rows drops what they decode to.  At world size
+    1 the collectives are skipped as in mode="obs"; pack, unpack and re-encode still run.
     """
 
-    def __init__(self, engine, group=None, depth=2, self_exchange=False):
+    def __init__(self, engine, group=None, depth=2, self_exchange=False, mode="obs", viewer=None):
         import torch
         import torch.distributed as dist
         self.torch = torch
@@ -220,6 +231,42 @@ class StepGather(object):
         self.skip = self.world == 1 and not self_exchange
         self.t = 0
         self.last = None
+        if mode not in ("obs", "state"):
+            raise ValueError("mode must be 'obs' or 'state'")
+        self.mode = mode
+        self.viewer = self.g_state = None
+        if mode == "state":
+            nb = engine.obs_state_layout()["rec_bytes"]
+            rows = self.world * self.m
+            self.g_state = [torch.zeros((rows, nb), dtype=torch.uint8, device=dev) for _ in range(self.depth)]
+            for k, out in enumerate(self.sets):  # the rank's records: its slice of the exchanged tensor
+                out.state = self.g_state[k][rank * self.m:(rank + 1) * self.m]
+            self._own_viewer = viewer is None
+            if viewer is None:
+                viewer = type(engine)(engine.builder.viewer(rows), device=dev.index)
+            if viewer.N != rows or viewer.obs_state_layout()["rec_bytes"] != nb:
+                raise ValueError("viewer must hold world * m = %d envs of the engine's record (%d bytes)" % (rows, nb))
+            self.viewer = viewer
+
+    def close(self):
+        """Free the viewer this object built (mode="state" without a viewer argument)."""
+        if self.viewer is not None and self._own_viewer:
+            self.viewer.close()
+        self.viewer = None
+
+    def _exchange(self, k, out):
+        """Set k's collectives (unless skipped) and, in mode="state", the viewer's unpack and re-encode, on
+        the current stream."""
+        if self.mode == "obs":
+            if not self.skip:
+                _all_gather_rows(self.g_obs[k], out.obs, self.group)
+                _all_gather_rows(self.g_flat[k], out.flat, self.group)
+            return
+        if not self.skip:
+            _all_gather_rows(self.g_state[k], out.state, self.group)
+            _all_gather_rows(self.g_flat[k], out.flat, self.group)
+        self.viewer.unpack_obs_state(self.g_state[k])
+        self.viewer.observe(out=self.g_obs[k])
 
     def step(self, run, after=None):
         """run(out) issues one engine step into output set `out` on the current stream; the step's
@@ -231,7 +278,10 @@ class StepGather(object):
         if self.pending[k] is not None:
             torch.cuda.current_stream(self.eng.device).wait_event(self.pending[k])
         run(out)
+        if self.mode == "state":
+            self.eng.pack_obs_state(out=out.state)
         if self.skip:
+            self._exchange(k, out)
             if after is not None:
                 after(k)
         elif self.comm is not None:
@@ -239,16 +289,14 @@ class StepGather(object):
             done.record(torch.cuda.current_stream(self.eng.device))
             self.comm.wait_event(done)
             with torch.cuda.stream(self.comm):
-                _all_gather_rows(self.g_obs[k], out.obs, self.group)
-                _all_gather_rows(self.g_flat[k], out.flat, self.group)
+                self._exchange(k, out)
                 if after is not None:
                     after(k)
                 ev = torch.cuda.Event()
                 ev.record(self.comm)
             self.pending[k] = ev
         else:
-            _all_gather_rows(self.g_obs[k], out.obs, self.group)
-            _all_gather_rows(self.g_flat[k], out.flat, self.group)
+            self._exchange(k, out)
             if after is not None:
                 after(k)
         self.last = k
