@@ -119,10 +119,10 @@ extern "C" {
 
 #define ZS_FLAG_VIEWER 8u    /* a viewer handle: it holds other handles' envs for encoding (zs_obs_state_unpack,
                               * zs_observe).  zs_create allocates it like any other handle.  zs_seed, zs_reset,
-                              * zs_step*, zs_gen_actions, zs_set_state, zs_set_rng and the zs_host_* calls
-                              * return ZS_ESTATE on it before any launch; zs_observe, zs_obs_shape, zs_describe,
-                              * zs_state_size, zs_get_state, zs_overflow, zs_destroy and the zs_obs_state_*
-                              * calls work on it */
+                              * zs_step*, zs_gen_actions, zs_set_state, zs_set_rng, zs_restore and the
+                              * zs_host_* calls return ZS_ESTATE on it before any launch; zs_observe,
+                              * zs_obs_shape, zs_describe, zs_state_size, zs_get_state, zs_overflow, zs_destroy,
+                              * zs_snapshot, zs_snapshot_layout and the zs_obs_state_* calls work on it */
 
 /* ---- range flags (zs_overflow) -------------------------------------------
  * The reference's obstacle life is an unbounded Python int that carries over resets
@@ -331,6 +331,50 @@ int zs_overflow(zs_handle* h, uint32_t* flags_host, int32_t clear, void* stream)
 int zs_obs_state_layout(const zs_handle* h, int32_t out[12]);
 int zs_obs_state_pack(zs_handle* h, void* rec_dev, void* stream);
 int zs_obs_state_unpack(zs_handle* h, const void* rec_dev, int32_t rec_bytes, int32_t env0, int32_t n, void* stream);
+
+/* ---- snapshot records: batched device snapshot, restore and clone of env state ---------------------
+ * A snapshot record is a verbatim copy of everything per-env that a later step, reset, respawn or
+ * observation reads, in one block of rec_bytes bytes (a multiple of 16); nothing is narrowed or re-derived.
+ * Restoring it and replaying the same actions reproduces the run bit for bit.  Sections, in record order
+ * (E entity slots, A agents, O obstacles, DW = ceil(W*H/32), OW = ceil(O/32)):
+ *   ring u32 [1248] (two MT19937 blocks), dead u32 [DW], obst_hp i32 [O] (int32 whatever the observation
+ *   dtype), obst_present u32 [OW], obst_nonpos u32 [OW], pos i32 [E] (x | y << 16), life i32 [E], serial u32 [E],
+ *   scal i32 [9] (t, deaths, zombie_deaths, episode_steps, n_order, needs_reset, reward prev zombie_deaths,
+ *   spawn serial counter, obstacle-cleanup flag), hp_dirty u32, dead_dirty u32, rngst u32 (MT19937 ring offset
+ *   | slot << 10 | next-block-ready << 11), prev_life i32 [A], weapon u8 [E], present u8 [E], order u8 [E],
+ *   listed u8 [A], zero padding.
+ * NOT in a record: the action-stream seed (zs_seed sets it; it belongs to the slot's policy), the death and
+ * action logs (a step's outputs: zs_restore empties them for the envs it writes), the handle's sticky
+ * ZS_OVF_* word, and zs_step_graph's policy step counter.
+ *
+ * zs_snapshot_layout: out[0] = rec_bytes; out[1..17] = the byte offsets of the 17 sections in the order
+ * above; out[18] = offset of the zero padding; out[19], out[20] = low and high word of the handle's 64-bit
+ * fingerprint; out[21] = scalar rows (9); out[22] = ring words (1248); out[23] = 0.  Two handles whose
+ * fingerprints agree can exchange records.  The fingerprint covers the map size, the entity counts (agents,
+ * bots, zombie slots), rules, reward mode, max_episode_steps, initial and minimum zombies and the static
+ * tables (obstacle cells and kinds, spawn lists, objective cells, agent weapons, bot types); not the env
+ * count, the observation settings, the flags, lanes_per_env or the launch overrides.
+ *
+ * zs_snapshot: record k of rec_dev ([n][rec_bytes], 16-byte aligned) = env env_idx_dev[k] (NULL: env k);
+ * duplicates allowed.  Every byte of a record is written (padding: zeros), nothing outside the n records.
+ * Any handle, viewers included.
+ * zs_restore: record src_idx_dev[k] (NULL: k) of the n_records records at rec_dev is written into env
+ * dst_idx_dev[k] (NULL: k), k < n.  n_records is the caller's declaration of how many records rec_dev
+ * holds: the kernel reads no record at or past it.  Destinations must be distinct (the caller's contract);
+ * sources may repeat (fan-out).  Envs that are no destination keep every byte.  After the copy the pending-
+ * reset list the next zs_step drains is rebuilt from the needs_reset flags of all N envs: an env restored
+ * from a pending record is reset by the next step, exactly once, and reported in reset_dev; a pending env
+ * overwritten by a running record is not reset.  The list parity does not change, so zs_step_graph's cached
+ * graphs stay valid.  ZS_ESTATE on a viewer handle.
+ * Both: asynchronous on `stream` (no host synchronisation, no host staging).  n < 0, n_records < 0, an
+ * unaligned rec_dev or a rec_bytes that is not the handle's: ZS_EINVAL before any launch.  Index entries
+ * are bounds-checked on the device: an entry whose env is outside [0, N), or whose record is outside
+ * [0, n_records), is skipped (nothing read or written for it).  Record contents are not validated.
+ * zs_set_state's needs_reset refusal is unchanged. */
+int zs_snapshot_layout(const zs_handle* h, int32_t out[24]);
+int zs_snapshot(zs_handle* h, const int32_t* env_idx_dev, int32_t n, void* rec_dev, void* stream);
+int zs_restore(zs_handle* h, const void* rec_dev, int32_t rec_bytes, int32_t n_records, const int32_t* src_idx_dev,
+               const int32_t* dst_idx_dev, int32_t n, void* stream);
 
 /* Diagnostics (not part of the reference surface): when enabled, every k_tick
  * (the step kernel), k_obs (the observation kernel) and k_reset (world rebuild)

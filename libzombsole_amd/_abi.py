@@ -76,6 +76,64 @@ def obs_state_record_dtype(obs_dtype, obs_encoding):
     return DTYPE_I32 if obs_dtype == DTYPE_I16 and obs_encoding != ENC_CHANNELS else obs_dtype
 
 
+SNAPSHOT_NSCAL, SNAPSHOT_RING = 9, 1248  # the per-env scalar rows, the words of both MT19937 blocks
+SNAPSHOT_SECTIONS = ("ring", "dead", "obst_hp", "obst_present", "obst_nonpos", "pos", "life", "serial", "scal", "hp_dirty",
+                     "dead_dirty", "rngst", "prev_life", "weapon", "present", "order", "listed")
+
+
+def snapshot_section_bytes(E, O, DW, OW, A):
+    """The size in bytes of every section of a snapshot record, in SNAPSHOT_SECTIONS' order."""
+    return (4 * SNAPSHOT_RING, 4 * DW, 4 * O, 4 * OW, 4 * OW, 4 * E, 4 * E, 4 * E, 4 * SNAPSHOT_NSCAL, 4, 4, 4, 4 * A,
+            E, E, E, A)
+
+
+def snapshot_layout(E, O, DW, OW, A):
+    """Mirror of snapshot_layout() (csrc/zs_snapshot.hpp): the byte offset of every section of an env's snapshot
+    record, "pad" (where the zero padding starts) and "rec_bytes" (a multiple of 16)."""
+    L, o = {}, 0
+    for name, nbytes in zip(SNAPSHOT_SECTIONS, snapshot_section_bytes(E, O, DW, OW, A)):
+        L[name] = o
+        o += nbytes
+    L["pad"] = o
+    L["rec_bytes"] = (o + 15) // 16 * 16
+    return L
+
+
+_M64 = (1 << 64) - 1
+
+
+def _fp_add(h, v):
+    z = ((h ^ (v & _M64)) + 0x9E3779B97F4A7C15) & _M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
+def _fp_table(h, values):
+    h = _fp_add(h, len(values))
+    for v in values:
+        h = _fp_add(h, int(v) & 0xffffffff)
+    return h
+
+
+def snapshot_fingerprint(cfg):
+    """Mirror of snapshot_fingerprint() (csrc/zs_snapshot.hpp) over a zs_config: handles whose fingerprints agree
+    can exchange snapshot records."""
+    m = cfg.map
+    Z = max(cfg.initial_zombies, cfg.minimum_zombies)
+    h = 0x7A735F736E617031
+    h = _fp_table(h, [m.width, m.height, m.n_obstacles, cfg.num_agents + cfg.num_bots + Z, cfg.num_agents, cfg.num_bots,
+                      Z, cfg.rules, cfg.reward_mode, cfg.max_episode_steps, cfg.initial_zombies, cfg.minimum_zombies])
+    h = _fp_table(h, m.obstacle_xy[:2 * m.n_obstacles])
+    h = _fp_table(h, m.obstacle_kind[:m.n_obstacles])
+    h = _fp_table(h, m.player_spawn_xy[:2 * m.n_player_spawns])
+    h = _fp_table(h, m.zombie_spawn_xy[:2 * m.n_zombie_spawns])
+    h = _fp_table(h, m.objective_xy[:2 * m.n_objectives])
+    h = _fp_table(h, cfg.agent_weapons[:cfg.num_agents])
+    h = _fp_table(h, cfg.bot_types[:cfg.num_bots])
+    return h
+
+
 LAUNCH_FIELDS = ["fused", "fobs", "tick_waves", "lds_budget", "rw_need", "reset_wgs", "reset_stream", "reset_lists",
                  "reset_grid", "defer_respawn", "respawn_grid", "obs_pipe", "obs_lds", "obs_patch", "obs_ring",
                  "obs_ring_patch", "obs_gather", "obs_gather_stat", "obs_stat", "obs_win", "obs_wgs", "par_exec"]
@@ -244,6 +302,14 @@ class ConfigBuilder(object):
         E = c.num_agents + c.num_bots + max(c.initial_zombies, c.minimum_zombies)
         return obs_state_layout(E, m.n_obstacles, (m.width * m.height + 31) // 32, (m.n_obstacles + 31) // 32,
                                 obs_state_record_dtype(c.obs_dtype, c.obs_encoding))
+
+    def snapshot_layout(self):
+        """The snapshot record of this config's handles (zs_snapshot_layout without a device), with "fingerprint"."""
+        c, m = self.cfg, self.cfg.map
+        E = c.num_agents + c.num_bots + max(c.initial_zombies, c.minimum_zombies)
+        L = snapshot_layout(E, m.n_obstacles, (m.width * m.height + 31) // 32, (m.n_obstacles + 31) // 32, c.num_agents)
+        L["fingerprint"] = snapshot_fingerprint(c)
+        return L
 
     @property
     def num_agents(self):

@@ -7,7 +7,8 @@
 // persistent store streams, k_obs_gather for large maps, k_obs in general).  zs_step_graph replays
 // a step as a hipGraph.  k_seed / k_gen_actions / k_get_state / k_set_state are the small helpers
 // behind the ABI; k_obs_state_pack / k_obs_state_unpack move the observation encoders' inputs between
-// handles as per-env records (zs_obs_state.hpp).
+// handles as per-env records (zs_obs_state.hpp); k_snapshot / k_restore / k_pending_list move complete envs in
+// and out of records (zs_snapshot.hpp).
 //
 // Semantics follow the reference exactly (parity: tests/); every sqrt range
 // test of the reference is replaced by its exact integer d^2 equivalent.
@@ -25,6 +26,7 @@
 #include "zs_reset.hpp"
 #include "zs_obs.hpp"
 #include "zs_obs_state.hpp"
+#include "zs_snapshot.hpp"
 
 // ---------------------------------------------------------------------------
 // seeding: random.seed(int) (init_by_array over abs(n) in 32-bit little-endian words)
@@ -394,6 +396,135 @@ __global__ __launch_bounds__(256) void k_obs_state_unpack(Dev d, ObsStateLayout 
     obs_state_copy<false>(d, L, wpe, env0, n, (uint4*)rec);
 }
 
+// ---------------------------------------------------------------------------
+// snapshot records (zs_snapshot.hpp): k_snapshot copies everything per-env into one record per entry,
+// k_restore copies records back into envs, k_pending_list rebuilds the pending-reset list from the flags.
+// One 256-thread workgroup per entry (the MT ring alone is 312 chunks), grid-stride over entries, a record
+// walked in 16-B chunks.  The record side takes one 16-B access per chunk.  The engine side is described by
+// a section table (SnapTable, by value, staged in LDS so a lane can index it): element k of a section of env
+// e lies at base + e * estride + k * kstride, which covers the env-major rows ([N][row]: estride = the row's
+// bytes, kstride = the element's) and the [k][N] columns (estride = the element's bytes, kstride = N of them)
+// alike.  A chunk inside one row of 4-byte elements moves as 16 B when its engine address allows, else as
+// four dwords; the columns are dword gathers (they sit together in the record: one round of one lane
+// group); the u8 rows and the padding move by byte.
+// ---------------------------------------------------------------------------
+static_assert(ZS_SNAP_NSCAL == S_NSCAL && ZS_SNAP_RING == ZS_RING_WORDS, "zs_snapshot.hpp mirrors zs_device.hpp");
+
+struct SnapTable {
+    uint8_t* base[SNAP_NSEC];
+    size_t estride[SNAP_NSEC];  // bytes from env e's first element to env e + 1's
+    size_t kstride[SNAP_NSEC];  // bytes from element k to element k + 1 of one env
+    int off[SNAP_NSEC + 1];     // SnapshotLayout::off
+    int rec_bytes;
+};
+
+// the section of record byte b, searching on from section s (sections are in record order; SNAP_NSEC: padding)
+__device__ __forceinline__ int snap_find(const SnapTable& T, int b, int s) {
+    while (s < SNAP_NSEC && b >= T.off[s + 1]) s++;
+    return s;
+}
+// the engine-side address of record byte b (the first byte of an element) of section s, env e
+__device__ __forceinline__ uint8_t* snap_addr(const SnapTable& T, int s, size_t e, int b) {
+    const int k = (b - T.off[s]) >> (s < SNAP_NWORD ? 2 : 0);
+    return T.base[s] + e * T.estride[s] + (size_t)k * T.kstride[s];
+}
+
+__device__ __forceinline__ void snap_stage_table(const SnapTable& arg, SnapTable* lds) {
+    static_assert(sizeof(SnapTable) % 4 == 0, "dword copy");
+    const uint32_t* src = (const uint32_t*)&arg;
+    for (int k = threadIdx.x; k < (int)(sizeof(SnapTable) / 4); k += blockDim.x) ((uint32_t*)lds)[k] = src[k];
+    __syncthreads();
+}
+
+// one record <-> env e, by the 256 threads of a workgroup; PACK: engine -> record, else record -> engine
+template <bool PACK>
+__device__ __forceinline__ void snapshot_copy(const SnapTable& T, uint4* row, size_t e) {
+    const int nch = T.rec_bytes >> 4;
+    for (int c = threadIdx.x; c < nch; c += 256) {
+        const int b0 = c << 4;
+        uint32_t w[4] = {0u, 0u, 0u, 0u};
+        if (!PACK) {
+            const uint4 v = row[c];
+            w[0] = v.x, w[1] = v.y, w[2] = v.z, w[3] = v.w;
+        }
+        int s = snap_find(T, b0, 0);
+        if (s < SNAP_NWORD && T.kstride[s] == 4 && b0 + 16 <= T.off[s + 1]) {  // inside one row of dwords
+            uint8_t* p = snap_addr(T, s, e, b0);
+            if (((uintptr_t)p & 15) == 0) {
+                if (PACK) row[c] = *(const uint4*)p;
+                else *(uint4*)p = uint4{w[0], w[1], w[2], w[3]};
+                continue;
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const int b = b0 + 4 * j;
+            s = snap_find(T, b, s);
+            if (s < SNAP_NWORD) {  // a dword of a 4-byte section (their sizes are multiples of 4)
+                uint32_t* p = (uint32_t*)snap_addr(T, s, e, b);
+                if (PACK) w[j] = *p;
+                else *p = w[j];
+                continue;
+            }
+            int sb = s;
+            for (int k = 0; k < 4; k++) {  // the u8 rows; padding packs as zero and restores nothing
+                sb = snap_find(T, b + k, sb);
+                if (sb == SNAP_NSEC) break;
+                uint8_t* p = snap_addr(T, sb, e, b + k);
+                if (PACK) w[j] |= (uint32_t)*p << (8 * k);
+                else *p = (uint8_t)(w[j] >> (8 * k));
+            }
+        }
+        if (PACK) row[c] = uint4{w[0], w[1], w[2], w[3]};
+    }
+}
+
+// record k = env idx[k] (idx NULL: env k); an index outside [0, N) is skipped
+__global__ __launch_bounds__(256) void k_snapshot(SnapTable tab, int N, const int32_t* idx, int n, uint4* rec) {
+    __shared__ SnapTable T;
+    snap_stage_table(tab, &T);
+    const int nch = T.rec_bytes >> 4;
+    for (int k = blockIdx.x; k < n; k += gridDim.x) {
+        const int e = idx ? idx[k] : k;
+        if ((unsigned)e >= (unsigned)N) continue;
+        snapshot_copy<true>(T, rec + (size_t)k * nch, (size_t)e);
+    }
+}
+
+// record src[k] (NULL: k) of the n_records at rec into env dst[k] (NULL: k); an entry whose record or env is out
+// of range is skipped.  The written envs' log counts are zeroed (the logs are a step's outputs), and *list_count
+// for k_pending_list, which follows on the stream.
+__global__ __launch_bounds__(256) void k_restore(SnapTable tab, int N, int32_t* dlog_n, int32_t* alog_n, const int32_t* src,
+                                                 const int32_t* dst, int n, int n_records, const uint4* rec, int* list_count) {
+    __shared__ SnapTable T;
+    snap_stage_table(tab, &T);
+    if (blockIdx.x == 0 && threadIdx.x == 0) *list_count = 0;
+    const int nch = T.rec_bytes >> 4;
+    for (int k = blockIdx.x; k < n; k += gridDim.x) {
+        const int r = src ? src[k] : k, e = dst ? dst[k] : k;
+        if ((unsigned)r >= (unsigned)n_records || (unsigned)e >= (unsigned)N) continue;
+        snapshot_copy<false>(T, (uint4*)rec + (size_t)r * nch, (size_t)e);
+        if (threadIdx.x == 0 && dlog_n) dlog_n[e] = 0, alog_n[e] = 0;
+    }
+}
+
+// list = the envs whose S_NEEDRESET is set, in any order (envs are independent); *count starts at zero
+// (k_restore).  One atomic per wave: its flagged lanes take consecutive entries.
+__global__ __launch_bounds__(256) void k_pending_list(const int32_t* needs_reset, int N, int* list, int* count) {
+    const int lane = threadIdx.x & 63;
+    for (int e0 = (blockIdx.x * 256 + threadIdx.x) - lane; e0 < N; e0 += gridDim.x * 256) {
+        const int e = e0 + lane;
+        const bool f = e < N && needs_reset[e] != 0;
+        const unsigned long long m = __ballot(f);
+        if (!m) continue;
+        int base = 0;
+        if (lane == 0) base = atomicAdd(count, __popcll(m));
+        base = __shfl(base, 0);
+        const int k = base + __popcll(m & ((1ull << lane) - 1ull));
+        if (f && (unsigned)k < (unsigned)N) list[k] = e;
+    }
+}
+
 __global__ void k_init_pending(Dev d, int* list, int* count) {
     int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e == 0) {
@@ -472,6 +603,7 @@ struct zs_handle {
     int* d_rlist[2];
     int* d_rcount;  // [2]
     int rpar = 0;
+    uint64_t snap_fp = 0;  // snapshot_fingerprint() of the config (zs_snapshot.hpp)
     // the drop-ins' per-call path (zs_host_*), set up by its first call: one pinned, device-mapped input
     // block (actions, then the `random` state as rings + st words) the kernels read in place, one pinned,
     // device-mapped record block k_host_pack writes in place, one synchronisation per call
@@ -877,6 +1009,7 @@ extern "C" int zs_create(const zs_config* cfg, int device, zs_handle** out) {
     if (cfg->launch) h->ov = *cfg->launch;
     h->cfg.launch = nullptr;
     h->device = device;
+    h->snap_fp = snapshot_fingerprint(cfg);
     const zs_map_desc& m = cfg->map;
     Dev& d = h->d;
     memset(&d, 0, sizeof(d));
@@ -1423,6 +1556,93 @@ extern "C" int zs_obs_state_unpack(zs_handle* h, const void* rec_dev, int32_t re
     unsigned grid;
     obs_state_geometry(L, n, &wpe, &grid);
     hipLaunchKernelGGL(k_obs_state_unpack, dim3(grid), dim3(256), 0, s, h->d, L, wpe, env0, n, (const uint4*)rec_dev);
+    HIPCHK(hipGetLastError());
+    return ZS_OK;
+}
+
+// ---------------------------------------------------------------------------
+// snapshot records (zs_snapshot.hpp; kernels above): asynchronous, no host staging
+// ---------------------------------------------------------------------------
+static SnapshotLayout handle_snapshot_layout(const zs_handle* h) {
+    const Dev& d = h->d;
+    return snapshot_layout(d.E, d.O, d.DW, d.OW, d.A);
+}
+
+static SnapTable snap_table(const zs_handle* h, const SnapshotLayout& L) {
+    const Dev& d = h->d;
+    const size_t N = d.N;
+    SnapTable T;
+    void* const base[SNAP_NSEC] = {d.ring, d.dead, d.obst_hp, d.obst_present, d.obst_nonpos, d.pos, d.life, d.serial,
+                                   d.scal, d.hp_dirty, d.dead_dirty, d.rngst, d.prev_life,
+                                   d.weapon, d.present, d.order, d.listed};
+    // elements per env of the env-major rows; 0: a [k][N] column array
+    const size_t row[SNAP_NSEC] = {ZS_RING_WORDS, (size_t)d.DW, (size_t)d.O, (size_t)d.OW, (size_t)d.OW, (size_t)d.E, (size_t)d.E, (size_t)d.E,
+                                   0, 0, 0, 0, 0,
+                                   (size_t)d.E, (size_t)d.E, (size_t)d.E, 0};
+    for (int s = 0; s < SNAP_NSEC; s++) {
+        const size_t es = s < SNAP_NWORD ? 4 : 1;
+        T.base[s] = (uint8_t*)base[s];
+        T.estride[s] = row[s] ? row[s] * es : es;
+        T.kstride[s] = row[s] ? es : N * es;
+        T.off[s] = L.off[s];
+    }
+    T.off[SNAP_NSEC] = L.off[SNAP_NSEC];
+    T.rec_bytes = L.rec_bytes;
+    return T;
+}
+
+extern "C" int zs_snapshot_layout(const zs_handle* h, int32_t out[24]) {
+    if (!h || !out) return fail(ZS_EINVAL, "null argument");
+    const SnapshotLayout L = handle_snapshot_layout(h);
+    static_assert(SNAP_NSEC + 7 == 24, "out[24]");
+    std::memset(out, 0, 24 * sizeof(int32_t));
+    out[0] = L.rec_bytes;
+    for (int s = 0; s <= SNAP_NSEC; s++) out[1 + s] = L.off[s];
+    out[SNAP_NSEC + 2] = (int32_t)(uint32_t)h->snap_fp;
+    out[SNAP_NSEC + 3] = (int32_t)(uint32_t)(h->snap_fp >> 32);
+    out[SNAP_NSEC + 4] = ZS_SNAP_NSCAL;
+    out[SNAP_NSEC + 5] = ZS_SNAP_RING;
+    return ZS_OK;
+}
+
+// workgroups of a launch over n entries, one entry per workgroup at a time (grid-stride past 16 per CU)
+static unsigned snap_grid(int n) { return (unsigned)std::min(n, 256 * 16); }
+
+extern "C" int zs_snapshot(zs_handle* h, const int32_t* env_idx_dev, int32_t n, void* rec_dev, void* stream) {
+    if (!h || !rec_dev) return fail(ZS_EINVAL, "null argument");
+    if (n < 0) return fail(ZS_EINVAL, "n must be >= 0");
+    if ((uintptr_t)rec_dev & 15) return fail(ZS_EINVAL, "rec_dev must be 16-byte aligned");
+    if (n == 0) return ZS_OK;
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(hipSetDevice(h->device));
+    const SnapTable T = snap_table(h, handle_snapshot_layout(h));
+    hipLaunchKernelGGL(k_snapshot, dim3(snap_grid(n)), dim3(256), 0, s, T, h->d.N, env_idx_dev, n, (uint4*)rec_dev);
+    HIPCHK(hipGetLastError());
+    return ZS_OK;
+}
+
+extern "C" int zs_restore(zs_handle* h, const void* rec_dev, int32_t rec_bytes, int32_t n_records, const int32_t* src_idx_dev,
+                          const int32_t* dst_idx_dev, int32_t n, void* stream) {
+    if (!h || !rec_dev) return fail(ZS_EINVAL, "null argument");
+    NOT_ON_VIEWER(h, "zs_restore");
+    const SnapshotLayout L = handle_snapshot_layout(h);
+    if (rec_bytes != L.rec_bytes) return fail(ZS_EINVAL, "rec_bytes differs from the handle's (zs_snapshot_layout)");
+    if (n < 0 || n_records < 0) return fail(ZS_EINVAL, "n and n_records must be >= 0");
+    if ((uintptr_t)rec_dev & 15) return fail(ZS_EINVAL, "rec_dev must be 16-byte aligned");
+    if (n == 0) return ZS_OK;
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(hipSetDevice(h->device));
+    const Dev& d = h->d;
+    const SnapTable T = snap_table(h, L);
+    // the list the next step drains, rebuilt in place from the restored flags: the copy zeroes its count, the
+    // list launch refills it.  rpar stays, the list the next step appends to and the respawn list are empty
+    // between calls (zs_step's counter protocol), so cached step graphs stay valid.  No memset nodes (zs_step).
+    const int p = h->rpar;
+    hipLaunchKernelGGL(k_restore, dim3(snap_grid(n)), dim3(256), 0, s, T, d.N, d.dlog_n, d.alog_n, src_idx_dev, dst_idx_dev,
+                       n, n_records, (const uint4*)rec_dev, h->d_rcount + p);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_pending_list, dim3((unsigned)std::min(64, (d.N + 255) / 256)), dim3(256), 0, s,
+                       (const int32_t*)(d.scal + (size_t)S_NEEDRESET * d.N), d.N, h->d_rlist[p], h->d_rcount + p);
     HIPCHK(hipGetLastError());
     return ZS_OK;
 }

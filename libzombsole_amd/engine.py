@@ -16,7 +16,8 @@ SYMBOLS = ["zs_last_error", "zs_create", "zs_destroy", "zs_obs_shape", "zs_seed"
            "zs_gen_actions", "zs_step_graph", "zs_step_graph_n", "zs_state_size", "zs_get_state", "zs_set_state", "zs_get_rng", "zs_set_rng", "zs_overflow", "zs_profile", "zs_profile_read", "zs_describe",
            "zs_debug_stamps", "zs_debug_stamps_wg", "zs_debug_timeline", "zs_debug_lists", "zs_death_log", "zs_action_log",
            "zs_host_layout", "zs_host_step", "zs_host_reset", "zs_host_observe",
-           "zs_obs_state_layout", "zs_obs_state_pack", "zs_obs_state_unpack"]
+           "zs_obs_state_layout", "zs_obs_state_pack", "zs_obs_state_unpack",
+           "zs_snapshot_layout", "zs_snapshot", "zs_restore"]
 
 _lib = None
 
@@ -74,6 +75,9 @@ def load_library(path=None):
     L.zs_obs_state_layout.argtypes = [vp, C.POINTER(i32)]
     L.zs_obs_state_pack.argtypes = [vp, vp, vp]
     L.zs_obs_state_unpack.argtypes = [vp, vp, i32, i32, i32, vp]
+    L.zs_snapshot_layout.argtypes = [vp, C.POINTER(i32)]
+    L.zs_snapshot.argtypes = [vp, vp, i32, vp, vp]
+    L.zs_restore.argtypes = [vp, vp, i32, i32, vp, vp, i32, vp]
     for s in SYMBOLS:
         if s != "zs_last_error":
             getattr(L, s).restype = C.c_int
@@ -294,6 +298,78 @@ class Engine(object):
         rc = self.L.zs_obs_state_unpack(self.h, _ptr(rec), int(rec.shape[1]), int(env0), n, self._stream())
         if rc:
             _raise(self.L, rc, "zs_obs_state_unpack")
+
+    # -- snapshot records (zs_snapshot / zs_restore): complete envs, for checkpoints, rewinds and forks -------------
+    def snapshot_layout(self):
+        """zs_snapshot_layout as a dict: the byte offset of every section of an env's snapshot record (the names
+        of _abi.SNAPSHOT_SECTIONS), "pad", "rec_bytes" and "fingerprint" (handles whose fingerprints agree can
+        exchange records)."""
+        if getattr(self, "_snl", None) is None:
+            out = (C.c_int32 * 24)()
+            rc = self.L.zs_snapshot_layout(self.h, out)
+            if rc:
+                _raise(self.L, rc, "zs_snapshot_layout")
+            v = [int(x) for x in out]
+            L = dict(zip(("rec_bytes",) + _abi.SNAPSHOT_SECTIONS + ("pad",), v))
+            L["fingerprint"] = (v[19] & 0xffffffff) | ((v[20] & 0xffffffff) << 32)
+            self._snl = L
+        return self._snl
+
+    def _index(self, idx, what):
+        """None, or `idx` (a sequence or tensor of env / record numbers) as a contiguous int32 device tensor."""
+        t = self.torch
+        if idx is None:
+            return None
+        idx = t.as_tensor(idx)
+        if idx.dim() != 1 or idx.dtype in (t.bool, t.float16, t.float32, t.float64):
+            raise ValueError("%s: an index is a 1-D integer tensor or sequence" % what)
+        return idx.to(device=self.device, dtype=t.int32).contiguous()
+
+    def _check_snapshot(self, rec, what, rows=0):
+        t = self.torch
+        nb = self.snapshot_layout()["rec_bytes"]
+        if (rec.dtype != t.uint8 or rec.dim() != 2 or rec.shape[1] != nb or not rec.is_contiguous() or
+                rec.device != self.device or rec.shape[0] < rows or rec.data_ptr() % 16):
+            raise ValueError("%s: records are a contiguous, 16-byte aligned uint8 tensor [rows >= %d, %d] on %s"
+                             % (what, rows, nb, self.device))
+
+    def snapshot(self, envs=None, out=None):
+        """The snapshot records of `envs` (default: all N, in order; duplicates allowed) as uint8 [n, rec_bytes]
+        (into the first n rows of `out` when given).  Asynchronous on the current stream."""
+        idx = self._index(envs, "snapshot")
+        n = self.N if idx is None else int(idx.shape[0])
+        if out is None:
+            out = self.torch.empty((n, self.snapshot_layout()["rec_bytes"]), dtype=self.torch.uint8, device=self.device)
+        self._check_snapshot(out, "snapshot", n)
+        rc = self.L.zs_snapshot(self.h, _ptr(idx), n, _ptr(out), self._stream())
+        if rc:
+            _raise(self.L, rc, "zs_snapshot")
+        return out[:n]
+
+    def restore(self, rec, src=None, dst=None, check=True):
+        """Record src[k] of `rec` (default: k) into env dst[k] (default: k), then the pending-reset list rebuilt
+        from the restored flags (zs_restore).  Sources may repeat, destinations must be distinct.  check=True
+        validates the indices on the host (one small synchronisation; ValueError on a record or env out of range,
+        a repeated destination, lengths that differ); check=False is the asynchronous path, on which the kernel
+        skips out-of-range entries and distinct destinations are the caller's contract."""
+        t = self.torch
+        self._check_snapshot(rec, "restore")
+        s, d = self._index(src, "restore"), self._index(dst, "restore")
+        n = int(s.shape[0]) if s is not None else int(d.shape[0]) if d is not None else int(rec.shape[0])
+        if s is not None and d is not None and s.shape[0] != d.shape[0]:
+            raise ValueError("restore: src and dst differ in length")
+        if check:
+            sv = s if s is not None else t.arange(n, device=self.device)
+            dv = d if d is not None else t.arange(n, device=self.device)
+            bad = ((sv < 0) | (sv >= rec.shape[0])).any() | ((dv < 0) | (dv >= self.N)).any()
+            dup = t.unique(dv).numel() != n if n else False
+            if bool(bad):
+                raise ValueError("restore: a record outside [0, %d) or an env outside [0, %d)" % (rec.shape[0], self.N))
+            if dup:
+                raise ValueError("restore: a destination env is repeated")
+        rc = self.L.zs_restore(self.h, _ptr(rec), int(rec.shape[1]), int(rec.shape[0]), _ptr(s), _ptr(d), n, self._stream())
+        if rc:
+            _raise(self.L, rc, "zs_restore")
 
     def gen_actions(self, step, n_discrete, out=None):
         o = self.actions if out is None else out

@@ -29,6 +29,38 @@ def shard_range(total_envs, rank, world):
     return env0, n
 
 
+CHECKPOINT_KEYS = ("records", "fingerprint", "rec_bytes", "num_envs", "env0", "base_seed")
+
+
+def write_checkpoint(path, records, fingerprint, num_envs, env0=0, base_seed=0):
+    """torch.save of a checkpoint: `records` (uint8 [num_envs, rec_bytes], any device; stored on the CPU) with what
+    load needs to refuse a file of another configuration.  Plain tensors in, no engine."""
+    import torch
+    if records.dim() != 2 or records.dtype != torch.uint8 or records.shape[0] != int(num_envs):
+        raise ValueError("write_checkpoint: records must be uint8 [num_envs = %d, rec_bytes]" % int(num_envs))
+    torch.save({"records": records.detach().cpu().contiguous(), "fingerprint": int(fingerprint),
+                "rec_bytes": int(records.shape[1]), "num_envs": int(num_envs), "env0": int(env0),
+                "base_seed": int(base_seed)}, path)
+
+
+def read_checkpoint(path, fingerprint, rec_bytes, num_envs):
+    """torch.load of a write_checkpoint file, on the CPU.  ValueError when its fingerprint, record size or env
+    count is not the expected one (or the file is no checkpoint); returns the dict."""
+    import torch
+    ck = torch.load(path, map_location="cpu")
+    if not isinstance(ck, dict) or any(k not in ck for k in CHECKPOINT_KEYS):
+        raise ValueError("read_checkpoint: %s is not a checkpoint (keys %s)" % (path, ", ".join(CHECKPOINT_KEYS)))
+    rec = ck["records"]
+    if ck["fingerprint"] != int(fingerprint):
+        raise ValueError("read_checkpoint: fingerprint %#x, expected %#x: the checkpoint is of another map, entity "
+                         "counts, rules or static tables" % (ck["fingerprint"], int(fingerprint)))
+    if ck["rec_bytes"] != int(rec_bytes) or rec.dim() != 2 or rec.shape[1] != int(rec_bytes) or rec.dtype != torch.uint8:
+        raise ValueError("read_checkpoint: records of %d bytes, expected %d" % (ck["rec_bytes"], int(rec_bytes)))
+    if ck["num_envs"] != int(num_envs) or rec.shape[0] != int(num_envs):
+        raise ValueError("read_checkpoint: %d envs, expected %d" % (ck["num_envs"], int(num_envs)))
+    return ck
+
+
 class BatchedZombsole(object):
     def __init__(self, surface, num_envs, rules_name, player_names, map_name, agent_ids=None, agent_id=0,
                  initial_zombies=0, minimum_zombies=0, max_episode_steps=0, base_seed=0, env0=0,
@@ -103,6 +135,46 @@ class BatchedZombsole(object):
     def sample_actions(self, step):
         """The bench/parity uniform policy, generated on device (zs_gen_actions)."""
         return self.engine.gen_actions(step, self.n_discrete)
+
+    # -- snapshot, restore, clone, checkpoints (Engine.snapshot / restore: complete envs as device records) -----
+    def snapshot(self, envs=None):
+        """The snapshot records of `envs` (default: all), uint8 [n, rec_bytes] on the device."""
+        return self.engine.snapshot(envs)
+
+    def restore(self, snap, src=None, dst=None, observe=True, check=True):
+        """Record src[k] of `snap` (default: k) into env dst[k] (default: k); see Engine.restore.  observe=True
+        re-encodes the written envs (a masked observe) and returns self.obs, whose other rows are untouched."""
+        eng, t = self.engine, self.torch
+        eng.restore(snap, src, dst, check=check)
+        if not observe:
+            return None
+        mask = t.zeros(eng.N, dtype=t.uint8, device=eng.device)
+        if dst is None:
+            n = snap.shape[0] if src is None else len(src)
+            mask[:min(int(n), eng.N)] = 1
+        else:
+            d = eng._index(dst, "restore").long()
+            mask[d[(d >= 0) & (d < eng.N)]] = 1
+        return eng.observe(mask)
+
+    def clone(self, src, dst, observe=True):
+        """Env dst[k] becomes a copy of env src[k] (fork; sources may repeat).  The copy goes through records in a
+        scratch tensor, so overlapping src / dst sets are safe: every destination gets its source's state as it
+        was before the call."""
+        return self.restore(self.engine.snapshot(src), None, dst, observe=observe)
+
+    def save_checkpoint(self, path):
+        """Every env's snapshot record and what identifies the run (write_checkpoint) into `path`."""
+        L = self.engine.snapshot_layout()
+        write_checkpoint(path, self.engine.snapshot(), L["fingerprint"], self.num_envs, self.env0, self.base_seed)
+
+    def load_checkpoint(self, path, observe=True):
+        """Restore every env from a save_checkpoint file of the same configuration and env count (ValueError
+        otherwise, before the engine is touched).  The action-stream seeds are not part of a checkpoint: they are
+        this object's own (base_seed, env0)."""
+        L = self.engine.snapshot_layout()
+        ck = read_checkpoint(path, L["fingerprint"], L["rec_bytes"], self.num_envs)
+        return self.restore(ck["records"].to(self.engine.device), observe=observe)
 
     def close(self):
         self.engine.close()
