@@ -8,7 +8,7 @@
 // a step as a hipGraph.  k_seed / k_gen_actions / k_get_state / k_set_state are the small helpers
 // behind the ABI; k_obs_state_pack / k_obs_state_unpack move the observation encoders' inputs between
 // handles as per-env records (zs_obs_state.hpp); k_snapshot / k_restore / k_pending_list move complete envs in
-// and out of records (zs_snapshot.hpp).
+// and out of records (zs_snapshot.hpp) by the record walker of zs_record.hpp.
 //
 // Semantics follow the reference exactly (parity: tests/); every sqrt range
 // test of the reference is replaced by its exact integer d^2 equivalent.
@@ -27,6 +27,7 @@
 #include "zs_obs.hpp"
 #include "zs_obs_state.hpp"
 #include "zs_snapshot.hpp"
+#include "zs_record.hpp"
 
 // ---------------------------------------------------------------------------
 // seeding: random.seed(int) (init_by_array over abs(n) in 32-bit little-endian words)
@@ -102,10 +103,6 @@ __global__ void k_tail(Dev d) {
 // ---------------------------------------------------------------------------
 // state views (one env, one thread; test pokes)
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ int state_words(const Dev& d) {
-    return ZS_STATE_HEADER + ZS_STATE_ENTITY_WORDS * d.E + d.E + 2 * d.O + 2 * d.A + d.DW;
-}
-
 // env e's state record (layout: include/zombsole_mi355x.h), written by threads tid = 0..nt-1 of one workgroup
 // (every thread of the workgroup calls it)
 __device__ void state_record(const Dev& d, int e, int32_t* b, int tid, int nt) {
@@ -399,111 +396,48 @@ __global__ __launch_bounds__(256) void k_obs_state_unpack(Dev d, ObsStateLayout 
 // ---------------------------------------------------------------------------
 // snapshot records (zs_snapshot.hpp): k_snapshot copies everything per-env into one record per entry,
 // k_restore copies records back into envs, k_pending_list rebuilds the pending-reset list from the flags.
-// One 256-thread workgroup per entry (the MT ring alone is 312 chunks), grid-stride over entries, a record
-// walked in 16-B chunks.  The record side takes one 16-B access per chunk.  The engine side is described by
-// a section table (SnapTable, by value, staged in LDS so a lane can index it): element k of a section of env
-// e lies at base + e * estride + k * kstride, which covers the env-major rows ([N][row]: estride = the row's
-// bytes, kstride = the element's) and the [k][N] columns (estride = the element's bytes, kstride = N of them)
-// alike.  A chunk inside one row of 4-byte elements moves as 16 B when its engine address allows, else as
-// four dwords; the columns are dword gathers (they sit together in the record: one round of one lane
-// group); the u8 rows and the padding move by byte.
+// One 256-thread workgroup per entry (the MT ring alone is 312 chunks), grid-stride over entries; each kernel is a
+// loop over (record, 16-B chunk) that calls the record walker (zs_record.hpp: the section table and
+// rec_copy_chunk).  The table comes by value (the section search reads it there, in scalar registers) and is
+// staged in LDS so a lane can index it by section.
 // ---------------------------------------------------------------------------
 static_assert(ZS_SNAP_NSCAL == S_NSCAL && ZS_SNAP_RING == ZS_RING_WORDS, "zs_snapshot.hpp mirrors zs_device.hpp");
+static_assert(SNAP_NSEC <= REC_MAX_SEC, "a snapshot record's sections fit a table");
 
-struct SnapTable {
-    uint8_t* base[SNAP_NSEC];
-    size_t estride[SNAP_NSEC];  // bytes from env e's first element to env e + 1's
-    size_t kstride[SNAP_NSEC];  // bytes from element k to element k + 1 of one env
-    int off[SNAP_NSEC + 1];     // SnapshotLayout::off
-    int rec_bytes;
-};
-
-// the section of record byte b, searching on from section s (sections are in record order; SNAP_NSEC: padding)
-__device__ __forceinline__ int snap_find(const SnapTable& T, int b, int s) {
-    while (s < SNAP_NSEC && b >= T.off[s + 1]) s++;
-    return s;
-}
-// the engine-side address of record byte b (the first byte of an element) of section s, env e
-__device__ __forceinline__ uint8_t* snap_addr(const SnapTable& T, int s, size_t e, int b) {
-    const int k = (b - T.off[s]) >> (s < SNAP_NWORD ? 2 : 0);
-    return T.base[s] + e * T.estride[s] + (size_t)k * T.kstride[s];
-}
-
-__device__ __forceinline__ void snap_stage_table(const SnapTable& arg, SnapTable* lds) {
-    static_assert(sizeof(SnapTable) % 4 == 0, "dword copy");
+__device__ __forceinline__ void rec_stage_table(const RecTable& arg, RecTable* lds) {
+    static_assert(sizeof(RecTable) % 4 == 0, "dword copy");
     const uint32_t* src = (const uint32_t*)&arg;
-    for (int k = threadIdx.x; k < (int)(sizeof(SnapTable) / 4); k += blockDim.x) ((uint32_t*)lds)[k] = src[k];
+    for (int k = threadIdx.x; k < (int)(sizeof(RecTable) / 4); k += blockDim.x) ((uint32_t*)lds)[k] = src[k];
     __syncthreads();
 }
 
-// one record <-> env e, by the 256 threads of a workgroup; PACK: engine -> record, else record -> engine
-template <bool PACK>
-__device__ __forceinline__ void snapshot_copy(const SnapTable& T, uint4* row, size_t e) {
-    const int nch = T.rec_bytes >> 4;
-    for (int c = threadIdx.x; c < nch; c += 256) {
-        const int b0 = c << 4;
-        uint32_t w[4] = {0u, 0u, 0u, 0u};
-        if (!PACK) {
-            const uint4 v = row[c];
-            w[0] = v.x, w[1] = v.y, w[2] = v.z, w[3] = v.w;
-        }
-        int s = snap_find(T, b0, 0);
-        if (s < SNAP_NWORD && T.kstride[s] == 4 && b0 + 16 <= T.off[s + 1]) {  // inside one row of dwords
-            uint8_t* p = snap_addr(T, s, e, b0);
-            if (((uintptr_t)p & 15) == 0) {
-                if (PACK) row[c] = *(const uint4*)p;
-                else *(uint4*)p = uint4{w[0], w[1], w[2], w[3]};
-                continue;
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const int b = b0 + 4 * j;
-            s = snap_find(T, b, s);
-            if (s < SNAP_NWORD) {  // a dword of a 4-byte section (their sizes are multiples of 4)
-                uint32_t* p = (uint32_t*)snap_addr(T, s, e, b);
-                if (PACK) w[j] = *p;
-                else *p = w[j];
-                continue;
-            }
-            int sb = s;
-            for (int k = 0; k < 4; k++) {  // the u8 rows; padding packs as zero and restores nothing
-                sb = snap_find(T, b + k, sb);
-                if (sb == SNAP_NSEC) break;
-                uint8_t* p = snap_addr(T, sb, e, b + k);
-                if (PACK) w[j] |= (uint32_t)*p << (8 * k);
-                else *p = (uint8_t)(w[j] >> (8 * k));
-            }
-        }
-        if (PACK) row[c] = uint4{w[0], w[1], w[2], w[3]};
-    }
-}
-
 // record k = env idx[k] (idx NULL: env k); an index outside [0, N) is skipped
-__global__ __launch_bounds__(256) void k_snapshot(SnapTable tab, int N, const int32_t* idx, int n, uint4* rec) {
-    __shared__ SnapTable T;
-    snap_stage_table(tab, &T);
-    const int nch = T.rec_bytes >> 4;
+__global__ __launch_bounds__(256) void k_snapshot(RecTable tab, int N, const int32_t* idx, int n, uint4* rec) {
+    __shared__ RecTable T;
+    rec_stage_table(tab, &T);
+    const int nch = tab.rec_bytes >> 4;
     for (int k = blockIdx.x; k < n; k += gridDim.x) {
         const int e = idx ? idx[k] : k;
         if ((unsigned)e >= (unsigned)N) continue;
-        snapshot_copy<true>(T, rec + (size_t)k * nch, (size_t)e);
+        RecChunk* row = (RecChunk*)(rec + (size_t)k * nch);
+        for (int c = threadIdx.x; c < nch; c += 256) rec_copy_chunk<true>(tab, T, row, (size_t)e, c);
     }
 }
 
 // record src[k] (NULL: k) of the n_records at rec into env dst[k] (NULL: k); an entry whose record or env is out
 // of range is skipped.  The written envs' log counts are zeroed (the logs are a step's outputs), and *list_count
 // for k_pending_list, which follows on the stream.
-__global__ __launch_bounds__(256) void k_restore(SnapTable tab, int N, int32_t* dlog_n, int32_t* alog_n, const int32_t* src,
+__global__ __launch_bounds__(256) void k_restore(RecTable tab, int N, int32_t* dlog_n, int32_t* alog_n, const int32_t* src,
                                                  const int32_t* dst, int n, int n_records, const uint4* rec, int* list_count) {
-    __shared__ SnapTable T;
-    snap_stage_table(tab, &T);
+    __shared__ RecTable T;
+    rec_stage_table(tab, &T);
     if (blockIdx.x == 0 && threadIdx.x == 0) *list_count = 0;
-    const int nch = T.rec_bytes >> 4;
+    const int nch = tab.rec_bytes >> 4;
     for (int k = blockIdx.x; k < n; k += gridDim.x) {
         const int r = src ? src[k] : k, e = dst ? dst[k] : k;
         if ((unsigned)r >= (unsigned)n_records || (unsigned)e >= (unsigned)N) continue;
-        snapshot_copy<false>(T, (uint4*)rec + (size_t)r * nch, (size_t)e);
+        RecChunk* row = (RecChunk*)rec + (size_t)r * nch;
+        for (int c = threadIdx.x; c < nch; c += 256) rec_copy_chunk<false>(tab, T, row, (size_t)e, c);
         if (threadIdx.x == 0 && dlog_n) dlog_n[e] = 0, alog_n[e] = 0;
     }
 }
@@ -1568,27 +1502,13 @@ static SnapshotLayout handle_snapshot_layout(const zs_handle* h) {
     return snapshot_layout(d.E, d.O, d.DW, d.OW, d.A);
 }
 
-static SnapTable snap_table(const zs_handle* h, const SnapshotLayout& L) {
+// the engine-side table of a snapshot record (zs_record.hpp): the handle's arrays in record order
+static RecTable snapshot_table(const zs_handle* h) {
     const Dev& d = h->d;
-    const size_t N = d.N;
-    SnapTable T;
     void* const base[SNAP_NSEC] = {d.ring, d.dead, d.obst_hp, d.obst_present, d.obst_nonpos, d.pos, d.life, d.serial,
                                    d.scal, d.hp_dirty, d.dead_dirty, d.rngst, d.prev_life,
                                    d.weapon, d.present, d.order, d.listed};
-    // elements per env of the env-major rows; 0: a [k][N] column array
-    const size_t row[SNAP_NSEC] = {ZS_RING_WORDS, (size_t)d.DW, (size_t)d.O, (size_t)d.OW, (size_t)d.OW, (size_t)d.E, (size_t)d.E, (size_t)d.E,
-                                   0, 0, 0, 0, 0,
-                                   (size_t)d.E, (size_t)d.E, (size_t)d.E, 0};
-    for (int s = 0; s < SNAP_NSEC; s++) {
-        const size_t es = s < SNAP_NWORD ? 4 : 1;
-        T.base[s] = (uint8_t*)base[s];
-        T.estride[s] = row[s] ? row[s] * es : es;
-        T.kstride[s] = row[s] ? es : N * es;
-        T.off[s] = L.off[s];
-    }
-    T.off[SNAP_NSEC] = L.off[SNAP_NSEC];
-    T.rec_bytes = L.rec_bytes;
-    return T;
+    return snapshot_rec_table(base, d.E, d.O, d.DW, d.OW, d.A, (size_t)d.N);
 }
 
 extern "C" int zs_snapshot_layout(const zs_handle* h, int32_t out[24]) {
@@ -1615,7 +1535,7 @@ extern "C" int zs_snapshot(zs_handle* h, const int32_t* env_idx_dev, int32_t n, 
     if (n == 0) return ZS_OK;
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(hipSetDevice(h->device));
-    const SnapTable T = snap_table(h, handle_snapshot_layout(h));
+    const RecTable T = snapshot_table(h);
     hipLaunchKernelGGL(k_snapshot, dim3(snap_grid(n)), dim3(256), 0, s, T, h->d.N, env_idx_dev, n, (uint4*)rec_dev);
     HIPCHK(hipGetLastError());
     return ZS_OK;
@@ -1633,7 +1553,7 @@ extern "C" int zs_restore(zs_handle* h, const void* rec_dev, int32_t rec_bytes, 
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(hipSetDevice(h->device));
     const Dev& d = h->d;
-    const SnapTable T = snap_table(h, L);
+    const RecTable T = snapshot_table(h);
     // the list the next step drains, rebuilt in place from the restored flags: the copy zeroes its count, the
     // list launch refills it.  rpar stays, the list the next step appends to and the respawn list are empty
     // between calls (zs_step's counter protocol), so cached step graphs stay valid.  No memset nodes (zs_step).
