@@ -180,6 +180,43 @@ CONFIGS = [
           agent_id=0, initial_zombies=6, minimum_zombies=4, observation_scope="surroundings:7",
           observation_position_encoding="channels", agent_weapon="random", debug=True), [53], 120, 1, 50,
      {"events": True}),
+    # The ways an episode ends (tests/outcomes.py; test_golden_outcomes.py counts them in the fixture files), on
+    # the small maps of ./maps, 40 calls a seed.  The seeds are the first under which the reference's run holds
+    # the outcomes named here.
+    # safehouse won (every alive player on an objective), once on the step the TimeLimit truncates
+    ("term_safe_tiny_a2", "multi", "discrete",
+     dict(rules_name="safehouse", player_names=[], map_name="safe_tiny", agent_ids=["0", "1"],
+          initial_zombies=3, minimum_zombies=3), [0, 3], 40, 1, 6),
+    # safehouse won on the step the player off the objectives dies; safehouse lost
+    ("term_safe_crowd_a2", "multi", "discrete",
+     dict(rules_name="safehouse", player_names=[], map_name="safe_crowd", agent_ids=["0", "1"],
+          initial_zombies=4, minimum_zombies=4), [0, 4], 40, 1, 0),
+    # evacuation: the spawns touch only diagonally (not together); agents only, and with a bot (the walk over
+    # the alive players starts from the first alive bot)
+    ("term_evac_tiny_a4", "multi", "discrete",
+     dict(rules_name="evacuation", player_names=[], map_name="evac_tiny", agent_ids=["0", "1", "2", "3"],
+          initial_zombies=2, minimum_zombies=2), [0, 1], 40, 1, 6),
+    ("term_evac_tiny_bot_a2", "multi", "discrete",
+     dict(rules_name="evacuation", player_names=["terminator"], map_name="evac_tiny", agent_ids=["0", "1"],
+          initial_zombies=2, minimum_zombies=2), [0, 1], 40, 1, 6),
+    # evacuation among nine zombies with knives: lost with fewer than half alive; won with a dead member
+    ("term_evac_crowd_a4", "multi", "discrete",
+     dict(rules_name="evacuation", player_names=[], map_name="evac_crowd", agent_ids=["0", "1", "2", "3"],
+          initial_zombies=9, minimum_zombies=9, agent_weapons="knife"), [0, 1], 40, 1, 0),
+    # survival lost (every player dead) on both surfaces; the single one also truncates with the agent dead
+    # and the troll alive
+    ("term_surv_melee_a2", "multi", "discrete",
+     dict(rules_name="survival", player_names=[], map_name="melee", agent_ids=["0", "1"],
+          initial_zombies=14, minimum_zombies=14), [0, 1], 40, 1, 0),
+    ("term_surv_single_troll", "single", "discrete",
+     dict(rules_name="survival", player_names=["troll"], map_name="melee", agent_id=0, initial_zombies=14,
+          minimum_zombies=14, observation_scope="surroundings:7", observation_position_encoding="channels"),
+     [0, 1], 40, 1, 0),
+    # extermination with a minimum of one zombie and one zombie spawn cell: the last zombie dies and the
+    # respawn places one (the cell is free: the episode goes on) or none (an agent stands on it: won)
+    ("term_ext_one_spawn_a2", "multi", "discrete",
+     dict(rules_name="extermination", player_names=[], map_name="one_spawn", agent_ids=["0", "1"],
+          initial_zombies=1, minimum_zombies=1, agent_weapons="axe"), [0, 3], 40, 1, 8),
 ]
 
 

@@ -131,9 +131,11 @@ CONFIGS = {"pen_duo": (pen_duo, "rich", "tick"), "pen_quad": (pen_quad, "rich", 
            "melee_rich": (melee, "rich", "tick"), "fort_bots": (fort_bots, "rich", "k_respawn")}
 
 # (G, kernel) -> (config, the regimes the row claims, see REGIME_COUNTERS).  Entities: pen_duo 2, pen_ham 3,
-# pen_quad 4, pen_six 6, brawl9 9, c2 12, melee 18, fort_bots 18, c5 24, c4 54.  Episodes last five steps, too few
-# for anything to die, so a list holds one action per zombie and bot (they always act) and one per agent whose
-# action comes to something.
+# pen_quad 4, pen_six 6, brawl9 9, c2 12, melee 18, fort_bots 18, c5 24, c4 54.  A list holds one action per alive
+# zombie and bot (they always act) and one per agent whose action comes to something.  Things do die within the
+# five steps (the oracle counts 0 to 344 deaths a row), but next to nothing ends: of about 3 400 episodes two end
+# by a rule (both in brawl9), every other one is the five-step truncation, and G = 1, 2, 16, 32 and 64 never see
+# done = 1.  The ways an episode ends are the table of terminal_outcomes.py.
 _ROWS = {
     # G = 1: chunks of one action; more than two actions go to the leader
     (1, "k_step"): ("pen_duo", ("one_chunk", "two_chunk")),

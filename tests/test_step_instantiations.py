@@ -10,145 +10,14 @@ value done, truncated, listed or the reset flag can hold, so after the step ever
 have been written, and every guard byte must still be 0x5A (a partial workgroup's idle lanes are where a store
 past the last env would come from).
 """
-import numpy as np
 import pytest
 
 import step_instantiations as S
 import step_plan_table as T
 from libzombsole_amd import _abi
-from test_obs_instantiations import FILL, GUARD
+from step_runner import Band, GuardedStep, run_engines  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-class Band(object):
-    """A tensor of `shape` and `dtype` at byte GUARD of a 0x5A-filled byte tensor with GUARD bytes after it."""
-
-    def __init__(self, eng, shape, dtype):
-        torch = eng.torch
-        self.nbytes = int(np.prod(shape)) * torch.empty((), dtype=dtype).element_size()
-        self.raw = torch.full((GUARD + self.nbytes + GUARD,), FILL, dtype=torch.uint8, device=eng.device)
-        assert self.raw.data_ptr() % 16 == 0 and GUARD >= 64 and GUARD % 8 == 0
-        self.view = self.raw[GUARD:GUARD + self.nbytes].view(dtype).view(shape)
-        assert self.view.data_ptr() == self.raw.data_ptr() + GUARD
-
-    def guards_hold(self):
-        raw = self.raw.cpu().numpy()
-        return bool((raw[:GUARD] == FILL).all() and (raw[GUARD + self.nbytes:] == FILL).all())
-
-
-class GuardedStep(object):
-    """The output set of Engine.step / step_graph (obs, rewards, done, trunc, listed, was_reset) and the action
-    tensor, each but the observations (test_obs_instantiations.py guards those) inside its own Band."""
-    FLAGS = ("done", "trunc", "listed", "was_reset")
-
-    def __init__(self, eng):
-        torch = eng.torch
-        n, a = eng.N, eng.A
-        self.bands = {"rewards": Band(eng, (n, a if eng.multi else 1), torch.float64),
-                      "done": Band(eng, (n,), torch.uint8), "trunc": Band(eng, (n,), torch.uint8),
-                      "listed": Band(eng, (n, a), torch.uint8), "was_reset": Band(eng, (n,), torch.uint8),
-                      "actions": Band(eng, (n, a, 3), torch.int32)}
-        for k, b in self.bands.items():
-            setattr(self, k, b.view)
-        self.obs = eng.obs
-
-    def clear(self):
-        """0x5A over every output payload (not the actions, which the step reads)."""
-        for k, b in self.bands.items():
-            if k != "actions":
-                b.raw.fill_(FILL)
-
-    def check(self, what):
-        for k, b in self.bands.items():
-            assert b.guards_hold(), ("guard bytes written", k, what)
-        for k in self.FLAGS:  # every env's flags were stored
-            v = getattr(self, k).cpu().numpy()
-            assert (v != FILL).all(), ("flag bytes never written", k, what, np.argwhere(v == FILL)[:8].tolist())
-
-
-def run_engines(builders, make_oracle, seeds, steps, stream_row, graph=False, states_at=(), expect=None):
-    """One engine per builder (the same config and seeds under different launch overrides), stepped in lock step
-    and each compared with one OracleEnv per env at every step: the reset observation; observations, rewards
-    (bit-exact, the listed ones), done, truncated, the autoreset flag and `listed`; the canonical state of every
-    env at the steps `states_at`.  expect: per builder, the describe() fields it must report.  Returns per step
-    (1-based; index 0 unused) the number of envs the oracle reset and the number it respawned zombies in."""
-    import torch
-    from libzombsole_amd.engine import Engine
-    from oracle.oracle import OracleEnv
-
-    n = len(seeds)
-    engs, outs = [], []
-    for i, b in enumerate(builders):
-        eng = Engine(b)
-        if expect:
-            desc = eng.describe()
-            assert {k: desc[k] for k in expect[i]} == expect[i], (i, desc)
-        eng.seed(seeds)
-        engs.append(eng)
-        outs.append(GuardedStep(eng))
-    kinds = [o[2] for o in engs[0].builder.map.obstacles]
-    A = engs[0].A
-    refs = []
-    obs0 = [eng.reset().cpu().numpy() for eng in engs]
-    for k, s in enumerate(seeds):
-        o = OracleEnv(make_oracle(1))
-        o.seed(s)
-        exp = o.reset()
-        for i in range(len(engs)):
-            assert np.array_equal(obs0[i][k], exp), ("reset obs", i, k)
-        refs.append(o)
-    need = [False] * n
-    resets, respawns, respawned = [0] * (steps + 1), [0] * (steps + 1), [0] * n
-    for t in range(1, steps + 1):
-        got = []
-        for i, (eng, out) in enumerate(zip(engs, outs)):
-            out.clear()
-            if graph:  # the policy's actions are generated inside the replayed graph, into the guarded tensor
-                eng.step_graph(t, 7, out=out, actions=out.actions)
-            else:
-                if stream_row.stream == "discrete":
-                    eng.gen_actions(t, 7, out=out.actions)
-                else:
-                    out.actions.copy_(torch.from_numpy(stream_row.actions(seeds, t, A)))
-                eng.step(actions=out.actions, out=out)
-            torch.cuda.synchronize()
-            out.check((i, t))
-            got.append({k: getattr(out, k).cpu().numpy() for k in
-                        ("obs", "rewards", "done", "trunc", "listed", "was_reset", "actions")})
-        acts = got[0]["actions"]
-        for g in got[1:]:
-            assert np.array_equal(g["actions"], acts)
-        if stream_row.stream == "discrete":  # zs_gen_actions' stream is the oracle's (run_hashes, the CPU census)
-            assert np.array_equal(acts[::max(1, n // 3)], stream_row.actions(seeds[::max(1, n // 3)], t, A))
-        for k, o in enumerate(refs):
-            if need[k]:
-                exp, r, d, tr, lb = o.reset(), None, False, False, np.ones(A, bool)
-                need[k] = False
-                resets[t] += 1
-            else:
-                exp, r, d, tr, lb = o.step(acts[k])
-                need[k] = d or tr
-                c = o.census()["respawns"]
-                respawns[t] += c != respawned[k]
-                respawned[k] = c
-            for i, g in enumerate(got):
-                assert bool(g["was_reset"][k]) == (r is None), ("autoreset flag", i, k, t)
-                assert bool(g["done"][k]) == d and bool(g["trunc"][k]) == tr, ("flags", i, k, t)
-                assert np.array_equal(g["listed"][k].astype(bool), lb), ("listed", i, k, t)
-                if r is None:
-                    assert not g["rewards"][k].any(), ("rewards of a reset", i, k, t)
-                else:
-                    assert np.array_equal(g["rewards"][k][lb].view(np.uint64), r[:A][lb].view(np.uint64)), \
-                        ("rew", i, k, t, g["rewards"][k], r)
-                assert np.array_equal(g["obs"][k], exp), ("obs", i, k, t)
-        if t in states_at:
-            for i, eng in enumerate(engs):
-                for k, o in enumerate(refs):
-                    assert eng.get_state(k).canonical(kinds) == o.state(), ("state", i, k, t)
-    for eng in engs:
-        eng.close()
-    return resets, respawns
 
 
 ALL_ROWS = S.ROWS + S.SMALL_ROWS
