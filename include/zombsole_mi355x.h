@@ -376,6 +376,34 @@ int zs_snapshot(zs_handle* h, const int32_t* env_idx_dev, int32_t n, void* rec_d
 int zs_restore(zs_handle* h, const void* rec_dev, int32_t rec_bytes, int32_t n_records, const int32_t* src_idx_dev,
                const int32_t* dst_idx_dev, int32_t n, void* stream);
 
+/* ---- action masks of the discrete action tables ----------------------------------------------------
+ * mask_dev is uint8 [N][num_agents][8], 8-byte aligned (else ZS_EINVAL).  Byte k of agent a is 1 exactly when,
+ * on the env's current world (the one its observation shows), the reference would carry out game_actions[k]
+ * of the Discrete(6) / Discrete(7) tables (gym_env.py:328-351, gym/multiagent_env.py:259-285) for that agent,
+ * were its action the first one executed: Agent.next_step returns an action (players/agent.py:28-96) and
+ * World.thing_move / thing_attack / thing_heal log 'moved to', 'injured' or 'healed' (core.py:140-202).
+ *   0..3  move (0,1), (-1,0), (0,-1), (1,0): the destination is inside the map and World.things holds nothing
+ *         there: a present obstacle blocks whatever its life (one re-spawned destroyed stays until the
+ *         episode's first cleanup), so does a present zombie, bot or agent; bodies and objectives do not
+ *   4     attack_closest: a zombie is present and the closest one is within the agent's own weapon range
+ *   5     heal: 1
+ *   6     heal_closest (multi surface; 0 on the single one, whose table has 6 entries): no other bot or agent
+ *         is present, or the closest one is within HEALING_RANGE
+ *   7     0
+ * An agent that is not in the world (dead, or never placed) has eight zero bytes.  An env pending its reset
+ * shows the terminal world's masks, as its observation does.
+ *
+ * zs_action_mask: one launch on `stream` for the envs whose env_mask_dev byte is nonzero (NULL = all); other
+ * envs' bytes are untouched.  Any handle: a viewer's envs (zs_obs_state_unpack) hold everything the kernel
+ * reads, so it works there at no extra cost.
+ * zs_action_mask_bind: while a buffer is bound (non-NULL), every zs_step ends with a mask launch of all envs
+ * into it, after the observation / tail launch, so the masks show respawned zombies and a reset env's new
+ * world; zs_step_graph(_n) captures that launch with the step.  Binding another buffer or NULL drops the
+ * cached graphs (the next zs_step_graph recaptures).  A handle that never binds launches what it did before.
+ * The buffer must outlive the binding.  ZS_ESTATE on a viewer handle (nothing steps it). */
+int zs_action_mask(zs_handle* h, const uint8_t* env_mask_dev, void* mask_dev, void* stream);
+int zs_action_mask_bind(zs_handle* h, void* mask_dev_or_null);
+
 /* Diagnostics (not part of the reference surface): when enabled, every k_tick
  * (the step kernel), k_obs (the observation kernel) and k_reset (world rebuild)
  * launch is bracketed by HIP events on its stream.  zs_profile_read synchronizes
@@ -390,7 +418,8 @@ int zs_profile_read(zs_handle* h, double out[8]);
  * object, NUL-terminated and truncated to len bytes.  "obs_kernel" names the kernel of a step's
  * and an unmasked zs_reset's observations ("step launch": the step writes them itself),
  * "obs_kernel_masked" that of a zs_reset / zs_observe with an env mask, "obs_encoders"
- * ("patched", "select" or "") the encoders of k_obs_ring.  Returns ZS_OK. */
+ * ("patched", "select" or "") the encoders of k_obs_ring; "mask_kernel", "mask_grid", "mask_block" the
+ * action-mask launch (zs_action_mask) and "mask_bound" whether a buffer is bound.  Returns ZS_OK. */
 int zs_describe(zs_handle* h, char* buf, int32_t len);
 /* Diagnostics: out[0], out[1] = the two pending-reset list counts, out[2] = the deferred-respawn
  * count (after everything queued on stream), out[3] = the list parity the next step drains. */

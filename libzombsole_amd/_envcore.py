@@ -74,6 +74,7 @@ class EnvCore(object):
         self._actions = np.zeros((1, self.engine.A, 3), dtype=np.int32)
         self.last = None  # the last call's HostRecord
         self._rng_last = None  # its stream, packed
+        self._mask_buf = None  # action_masks()'s device tensor
         self.game = GameView(self.engine, 0, map_, rules_name, player_names, agent_ids, agent_weapons,
                              initial_zombies, minimum_zombies, debug)
         self.new_world(first=True)
@@ -162,6 +163,14 @@ class EnvCore(object):
         rec = self.engine.host_record()
         self.engine.host_observe(rec)
         return HostRecord(self.engine, rec[0], self._lay, self._np_obs).obs
+
+    def action_masks(self):
+        """The env's action masks, uint8 [A, n_discrete] on the host: the standalone mask launch (zs_action_mask)
+        and a copy.  Not part of the per-call record, whose launches and size stay as they are."""
+        eng = self.engine
+        if self._mask_buf is None:
+            self._mask_buf = self.torch.zeros((eng.N, eng.A, 8), dtype=self.torch.uint8, device=eng.device)
+        return eng.action_mask(out=self._mask_buf)[0, :, :eng.n_discrete].cpu().numpy()
 
     def close(self):
         self.engine.close()

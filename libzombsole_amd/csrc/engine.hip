@@ -7,7 +7,8 @@
 // persistent store streams, k_obs_gather for large maps, k_obs in general).  zs_step_graph replays
 // a step as a hipGraph.  k_seed / k_gen_actions / k_get_state / k_set_state are the small helpers
 // behind the ABI; k_obs_state_pack / k_obs_state_unpack move the observation encoders' inputs between
-// handles as per-env records (zs_obs_state.hpp); k_snapshot / k_restore / k_pending_list move complete envs in
+// handles as per-env records (zs_obs_state.hpp); k_action_mask (zs_mask.hpp, its own unit) writes the per-agent
+// action masks of the discrete tables, on request or as the last launch of every step; k_snapshot / k_restore / k_pending_list move complete envs in
 // and out of records (zs_snapshot.hpp) by the record walker of zs_record.hpp.
 //
 // Semantics follow the reference exactly (parity: tests/); every sqrt range
@@ -28,6 +29,7 @@
 #include "zs_obs_state.hpp"
 #include "zs_snapshot.hpp"
 #include "zs_record.hpp"
+#include "zs_mask.hpp"
 
 // ---------------------------------------------------------------------------
 // seeding: random.seed(int) (init_by_array over abs(n) in 32-bit little-endian words)
@@ -538,6 +540,7 @@ struct zs_handle {
     int* d_rcount;  // [2]
     int rpar = 0;
     uint64_t snap_fp = 0;  // snapshot_fingerprint() of the config (zs_snapshot.hpp)
+    void* mask_bound = nullptr;  // zs_action_mask_bind: every zs_step ends with a mask launch into it
     // the drop-ins' per-call path (zs_host_*), set up by its first call: one pinned, device-mapped input
     // block (actions, then the `random` state as rings + st words) the kernels read in place, one pinned,
     // device-mapped record block k_host_pack writes in place, one synchronisation per call
@@ -1268,10 +1271,56 @@ extern "C" int zs_step(zs_handle* h, const int32_t* actions_dev, void* obs_dev, 
     if (h->d.fobs || !obs_dev) {
         hipLaunchKernelGGL(k_tail, dim3(1), dim3(64), 0, s, h->d);
         const hipError_t le = hipGetLastError();
-        return le == hipSuccess ? ZS_OK : tail_on_error(fail(ZS_EHIP, std::string("k_tail: ") + hipGetErrorString(le)));
+        if (le != hipSuccess) return tail_on_error(fail(ZS_EHIP, std::string("k_tail: ") + hipGetErrorString(le)));
+    } else {
+        rc = launch_obs(h, obs_dev, nullptr, s);
+        if (rc) return tail_on_error(rc);
     }
-    rc = launch_obs(h, obs_dev, nullptr, s);
-    return rc ? tail_on_error(rc) : ZS_OK;
+    // 4) a bound mask buffer (zs_action_mask_bind): the masks of the world the observations show, respawned
+    //    zombies and reset envs included (the step's tail is done: nothing to undo when this launch fails)
+    if (h->mask_bound) {
+        const hipError_t me = launch_action_mask(s, h->d, nullptr, h->mask_bound);
+        if (me != hipSuccess) return fail(ZS_EHIP, std::string("k_action_mask: ") + hipGetErrorString(me));
+    }
+    return ZS_OK;
+}
+
+static int mask_buffer_ok(const void* mask_dev) {
+    if (((uintptr_t)mask_dev & 7u) != 0) return fail(ZS_EINVAL, "the action-mask buffer must be 8-byte aligned");
+    return ZS_OK;
+}
+
+// Action masks of the current state (zs_mask.hpp), uint8 [N][A][8].  Viewer handles included: the kernel reads
+// what zs_obs_state_unpack fills (pos, present, weapon, obstacle presence) and the static cell map.
+extern "C" int zs_action_mask(zs_handle* h, const uint8_t* env_mask_dev, void* mask_dev, void* stream) {
+    if (!h || !mask_dev) return fail(ZS_EINVAL, "null argument");
+    int rc = mask_buffer_ok(mask_dev);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(launch_action_mask(s, h->d, env_mask_dev, mask_dev));
+    return ZS_OK;
+}
+
+extern "C" int zs_action_mask_bind(zs_handle* h, void* mask_dev_or_null) {
+    if (!h) return fail(ZS_EINVAL, "null handle");
+    NOT_ON_VIEWER(h, "zs_action_mask_bind");
+    int rc = mask_buffer_ok(mask_dev_or_null);
+    if (rc) return rc;
+    if (mask_dev_or_null == h->mask_bound) return ZS_OK;
+    // the cached step graphs hold the old launch sequence (a rare call: wait for the ones in flight first)
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipDeviceSynchronize());
+    for (auto& gs : h->gsets) {
+        for (hipGraphExec_t& g : gs.g)
+            if (g) {
+                HIPCHK(hipGraphExecDestroy(g));
+                g = nullptr;
+            }
+        gs.used = 0;
+    }
+    h->mask_bound = mask_dev_or_null;
+    return ZS_OK;
 }
 
 extern "C" int zs_gen_actions(zs_handle* h, uint64_t step, int32_t n_discrete, int32_t* actions_dev, void* stream) {
@@ -1665,11 +1714,13 @@ extern "C" int zs_describe(zs_handle* h, char* buf, int32_t len) {
              "{\"envs\": %d, \"entities\": %d, \"lanes_per_env\": %d, \"step_kernel\": \"%s\", \"step_lds\": %d, "
              "\"step_wgs_per_cu\": %d, \"rng_window\": %d, \"obs_kernel\": \"%s\", \"reset_side_stream\": %d, "
              "\"reset_lds\": %d, \"respawn\": \"%s\", \"tick_waves\": %d, \"rng_step\": %d, \"par_exec\": %d, "
-             "\"obs_kernel_masked\": \"%s\", \"obs_encoders\": \"%s\"}",
+             "\"obs_kernel_masked\": \"%s\", \"obs_encoders\": \"%s\", \"mask_kernel\": \"k_action_mask\", "
+             "\"mask_grid\": %u, \"mask_block\": %d, \"mask_bound\": %d}",
              d.N, d.E, p.G, p.fused ? "k_step" : "k_tick", p.lds, p.resident, p.rw_cap,
              d.fobs ? "step launch" : obs_kernel_name(kf.kind), h->reset_side,
              p.reset_lds, p.defer_respawn ? "k_respawn" : "tick", p.tick_waves, p.rw_step,
-             d.par_exec, obs_kernel_name(h->obs.masked.kind), obs_encoders_name(kf));
+             d.par_exec, obs_kernel_name(h->obs.masked.kind), obs_encoders_name(kf), zs_mask_grid(d.N), ZS_MASK_BLOCK,
+             h->mask_bound ? 1 : 0);
     return ZS_OK;
 }
 

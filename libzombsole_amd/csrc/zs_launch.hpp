@@ -4,6 +4,7 @@
 //   k_tick_g.hip  once per lanes-per-env G (-DZS_G=1..64): k_tick<G, 5/6> and the fused k_step<G>
 //   k_obs_t.hip   once per observation dtype (-DZS_OBS_T=0/1/2): every observation kernel
 //   k_reset.hip   k_reset, k_respawn, k_list_filter
+//   k_mask.hip    k_action_mask (zs_mask.hpp)
 //   engine.hip    the C ABI and the small helper kernels (the launches are planned in zs_obs_plan.hpp, zs_step_plan.hpp)
 // Each unit exports plain host functions that launch its kernels; nothing but Dev, the observation
 // plan's ObsKernel (zs_obs_plan.hpp) and plain pointers crosses the units.
@@ -66,3 +67,7 @@ hipError_t launch_list_filter(unsigned grid, hipStream_t s, const int* src, cons
                               int* dst_count, const uint8_t* mask, int N);
 hipError_t reset_lds_attr(int bytes);
 hipError_t stamps_reset(unsigned long long* wg, int clear);
+
+// action masks (zs_mask.hpp): uint8 [N][A][8] into out, 8-byte aligned, for the envs whose env_mask byte is
+// nonzero (null: all)
+hipError_t launch_action_mask(hipStream_t s, const Dev& d, const uint8_t* env_mask, void* out);

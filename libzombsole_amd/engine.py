@@ -17,7 +17,8 @@ SYMBOLS = ["zs_last_error", "zs_create", "zs_destroy", "zs_obs_shape", "zs_seed"
            "zs_debug_stamps", "zs_debug_stamps_wg", "zs_debug_timeline", "zs_debug_lists", "zs_death_log", "zs_action_log",
            "zs_host_layout", "zs_host_step", "zs_host_reset", "zs_host_observe",
            "zs_obs_state_layout", "zs_obs_state_pack", "zs_obs_state_unpack",
-           "zs_snapshot_layout", "zs_snapshot", "zs_restore"]
+           "zs_snapshot_layout", "zs_snapshot", "zs_restore",
+           "zs_action_mask", "zs_action_mask_bind"]
 
 _lib = None
 
@@ -78,6 +79,8 @@ def load_library(path=None):
     L.zs_snapshot_layout.argtypes = [vp, C.POINTER(i32)]
     L.zs_snapshot.argtypes = [vp, vp, i32, vp, vp]
     L.zs_restore.argtypes = [vp, vp, i32, i32, vp, vp, i32, vp]
+    L.zs_action_mask.argtypes = [vp, vp, vp, vp]
+    L.zs_action_mask_bind.argtypes = [vp, vp]
     for s in SYMBOLS:
         if s != "zs_last_error":
             getattr(L, s).restype = C.c_int
@@ -170,6 +173,8 @@ class Engine(object):
         n = C.c_int32()
         self.L.zs_state_size(self.h, C.byref(n))
         self.state_words = int(n.value)
+        self.n_discrete = 7 if self.multi else 6
+        self.masks = None  # the bound action-mask tensor (bind_action_masks), uint8 [N, A, 8]
 
     def close(self):
         if getattr(self, "h", None) and self.h.value:
@@ -256,6 +261,43 @@ class Engine(object):
         if rc:
             _raise(self.L, rc, "zs_observe")
         return o
+
+    # -- action masks of the discrete tables (zs_action_mask*) ------------------------------------------------------
+    def _check_masks(self, m, what):
+        t = self.torch
+        if (m.dtype != t.uint8 or m.device != self.device or not m.is_contiguous() or m.data_ptr() % 8 or
+                tuple(m.shape) != (self.N, self.A, 8)):
+            raise ValueError("%s: masks are a contiguous, 8-byte aligned uint8 tensor [%d, %d, 8] on %s"
+                             % (what, self.N, self.A, self.device))
+
+    def action_mask(self, mask=None, out=None):
+        """The action masks of the current state, uint8 [N, A, 8] (zs_action_mask): entry k of agent a is 1 when
+        the reference would carry out discrete action k for it; entries at k >= n_discrete are 0, absent agents
+        all 0.  Envs where the uint8 device tensor `mask` is zero keep their bytes.  Into `out` when given, else
+        into the bound tensor, else into a tensor this call allocates (zeroed)."""
+        o = out if out is not None else self.masks
+        if o is None:
+            o = self.torch.zeros((self.N, self.A, 8), dtype=self.torch.uint8, device=self.device)
+        self._check_masks(o, "action_mask")
+        rc = self.L.zs_action_mask(self.h, _ptr(mask), _ptr(o), self._stream())
+        if rc:
+            _raise(self.L, rc, "zs_action_mask")
+        return o
+
+    def bind_action_masks(self, buf=True):
+        """Bind `buf` (True: a new tensor; None / False: unbind) so that every step(), step_graph() and
+        step_graphed() ends with a mask launch into it (zs_action_mask_bind); self.masks is the bound tensor."""
+        if buf is True:
+            buf = self.torch.zeros((self.N, self.A, 8), dtype=self.torch.uint8, device=self.device)
+        elif buf is False:
+            buf = None
+        if buf is not None:
+            self._check_masks(buf, "bind_action_masks")
+        rc = self.L.zs_action_mask_bind(self.h, _ptr(buf))
+        if rc:
+            _raise(self.L, rc, "zs_action_mask_bind")
+        self.masks = buf
+        return buf
 
     # -- observation-state records (zs_obs_state_*): what the encoders read of an env, a fraction of its observation
     def obs_state_layout(self):

@@ -94,6 +94,12 @@ class MultiagentZombsoleEnv(object):
     def get_observation(self):
         return self._observations(self._core.observe())
 
+    def action_masks(self):
+        """Not in the reference: uint8 [num_agents, 7] in possible_agents order, entry k of an agent is 1 when
+        MultiagentZombsoleEnvDiscreteAction.game_actions[k] would succeed for it on the current world; an agent
+        that is not in the world has all zeros (include/zombsole_mi355x.h, zs_action_mask)."""
+        return self._core.action_masks()
+
     def _process_single_agent_action(self, sp_action):
         coords = sp_action.get("parameter", [0, 0])
         return {"action_type": sp_action["action_type"], "parameter": coords}
@@ -169,6 +175,9 @@ class MultiAgentWrapper(object):
 
     def render(self):
         return self.env.render()
+
+    def action_masks(self):
+        return self.env.action_masks()
 
     def close(self):
         self.env.close()

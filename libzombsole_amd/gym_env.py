@@ -76,6 +76,11 @@ class ZombsoleGymEnv(Env):
     def get_frame_size(self):
         return tuple(self.observation_space.shape[1:3])
 
+    def action_masks(self):
+        """Not in the reference: uint8 [6], entry k is 1 when ZombsoleGymEnvDiscreteAction.game_actions[k] would
+        succeed for the agent on the current world (include/zombsole_mi355x.h, zs_action_mask)."""
+        return self._core.action_masks()[0]
+
     def step(self, action):
         """gym_env.py:99-145: set_action, World.step, reward, respawn, obs, rules, end reward."""
         self.game.agents[0].set_action(action)

@@ -66,7 +66,8 @@ class BatchedZombsole(object):
                  initial_zombies=0, minimum_zombies=0, max_episode_steps=0, base_seed=0, env0=0,
                  observation_scope="world", observation_position_encoding="simple", agent_weapon="rifle",
                  observation_surroundings_width=21, observation_position_encoding_style="channels",
-                 agent_weapons="rifle", obs_dtype=None, autoreset=True, device=None, lanes_per_env=0):
+                 agent_weapons="rifle", obs_dtype=None, autoreset=True, device=None, lanes_per_env=0,
+                 action_masks=False):
         if surface == "single":
             b = _abi.single_env_config(num_envs, rules_name, player_names, map_name, agent_id, initial_zombies,
                                        minimum_zombies, observation_scope, observation_position_encoding,
@@ -88,6 +89,18 @@ class BatchedZombsole(object):
         self.engine.seed([self.base_seed + self.env0 + i for i in range(self.num_envs)])
         self._triples = self.torch.from_numpy(DISCRETE_TRIPLES).to(self.engine.device)
         self.n_discrete = 7 if surface == "multi" else 6
+        # action_masks=True: a mask tensor bound to the engine, so every step ends with the mask launch; reset,
+        # restore, clone and load_checkpoint launch it themselves
+        if action_masks:
+            self.engine.bind_action_masks()
+
+    @property
+    def action_masks(self):
+        """uint8 [N, A, n_discrete] (a view of the engine's bound [N, A, 8] tensor): entry k of agent a is 1 when
+        discrete action k would succeed for it on the world self.obs shows; all 0 for an agent not in the world.
+        Valid after every reset, step, restore / clone and load_checkpoint.  None without action_masks=True."""
+        m = self.engine.masks
+        return None if m is None else m[:, :, :self.engine.n_discrete]
 
     @property
     def obs(self):
@@ -102,7 +115,10 @@ class BatchedZombsole(object):
         return self.engine.listed
 
     def reset(self, mask=None):
-        return self.engine.reset(mask)
+        obs = self.engine.reset(mask)
+        if self.engine.masks is not None:
+            self.engine.action_mask(mask)
+        return obs
 
     def discrete_to_triples(self, ids):
         """Discrete(6)/(7) ids [N, A] (gym_env.py:328-351, gym/multiagent_env.py:259-285) -> [N, A, 3]."""
@@ -146,7 +162,7 @@ class BatchedZombsole(object):
         re-encodes the written envs (a masked observe) and returns self.obs, whose other rows are untouched."""
         eng, t = self.engine, self.torch
         eng.restore(snap, src, dst, check=check)
-        if not observe:
+        if not observe and self.engine.masks is None:
             return None
         mask = t.zeros(eng.N, dtype=t.uint8, device=eng.device)
         if dst is None:
@@ -155,7 +171,9 @@ class BatchedZombsole(object):
         else:
             d = eng._index(dst, "restore").long()
             mask[d[(d >= 0) & (d < eng.N)]] = 1
-        return eng.observe(mask)
+        if self.engine.masks is not None:  # the written envs' action masks, beside their observations
+            eng.action_mask(mask)
+        return eng.observe(mask) if observe else None
 
     def clone(self, src, dst, observe=True):
         """Env dst[k] becomes a copy of env src[k] (fork; sources may repeat).  The copy goes through records in a
