@@ -123,6 +123,10 @@ extern "C" {
                               * zs_host_* calls return ZS_ESTATE on it before any launch; zs_observe,
                               * zs_obs_shape, zs_describe, zs_state_size, zs_get_state, zs_overflow, zs_destroy,
                               * zs_snapshot, zs_snapshot_layout and the zs_obs_state_* calls work on it */
+#define ZS_FLAG_ENV_PARAMS 16u /* per-env zombie counts and time limits (zs_env_params_set / _get): every env carries
+                                * (initial_zombies, minimum_zombies, max_episode_steps) twice, the triple its next
+                                * reset takes up and the triple of its running episode; both start as the config's
+                                * values, which are the caps.  zs_create refuses it on a viewer handle (ZS_ESTATE) */
 
 /* ---- range flags (zs_overflow) -------------------------------------------
  * The reference's obstacle life is an unbounded Python int that carries over resets
@@ -131,6 +135,8 @@ extern "C" {
 #define ZS_OVF_INT16 1u /* an obstacle life went below -32768: ZS_DTYPE_I16 observations saturate it */
 #define ZS_OVF_INT32 2u /* an obstacle life reached -2147483647 and saturated there: from then on
                          * that env differs from the reference */
+#define ZS_OVF_PARAM_RANGE 4u /* zs_env_params_set met an entry it did not apply: an env index outside [0, N), or
+                               * a value outside its range (the config's value is the cap) */
 
 /* ---- map description (parsed by the host; zombsole/game.py:45-97) ------- */
 typedef struct zs_map_desc {
@@ -342,18 +348,21 @@ int zs_obs_state_unpack(zs_handle* h, const void* rec_dev, int32_t rec_bytes, in
  *   scal i32 [9] (t, deaths, zombie_deaths, episode_steps, n_order, needs_reset, reward prev zombie_deaths,
  *   spawn serial counter, obstacle-cleanup flag), hp_dirty u32, dead_dirty u32, rngst u32 (MT19937 ring offset
  *   | slot << 10 | next-block-ready << 11), prev_life i32 [A], weapon u8 [E], present u8 [E], order u8 [E],
- *   listed u8 [A], zero padding.
+ *   listed u8 [A], zero padding.  A ZS_FLAG_ENV_PARAMS handle's record holds one section more, env_params
+ *   i32 [6] (the current triple, then the next one), after prev_life and before the byte rows.
  * NOT in a record: the action-stream seed (zs_seed sets it; it belongs to the slot's policy), the death and
  * action logs (a step's outputs: zs_restore empties them for the envs it writes), the handle's sticky
  * ZS_OVF_* word, and zs_step_graph's policy step counter.
  *
  * zs_snapshot_layout: out[0] = rec_bytes; out[1..17] = the byte offsets of the 17 sections in the order
  * above; out[18] = offset of the zero padding; out[19], out[20] = low and high word of the handle's 64-bit
- * fingerprint; out[21] = scalar rows (9); out[22] = ring words (1248); out[23] = 0.  Two handles whose
+ * fingerprint; out[21] = scalar rows (9); out[22] = ring words (1248); out[23] = the byte offset of the
+ * env_params section of a ZS_FLAG_ENV_PARAMS handle's record, else 0.  Two handles whose
  * fingerprints agree can exchange records.  The fingerprint covers the map size, the entity counts (agents,
  * bots, zombie slots), rules, reward mode, max_episode_steps, initial and minimum zombies and the static
  * tables (obstacle cells and kinds, spawn lists, objective cells, agent weapons, bot types); not the env
- * count, the observation settings, the flags, lanes_per_env or the launch overrides.
+ * count, the observation settings, lanes_per_env, the launch overrides or the flags, except ZS_FLAG_ENV_PARAMS
+ * (its record is longer), which it covers.
  *
  * zs_snapshot: record k of rec_dev ([n][rec_bytes], 16-byte aligned) = env env_idx_dev[k] (NULL: env k);
  * duplicates allowed.  Every byte of a record is written (padding: zeros), nothing outside the n records.
@@ -404,6 +413,39 @@ int zs_restore(zs_handle* h, const void* rec_dev, int32_t rec_bytes, int32_t n_r
 int zs_action_mask(zs_handle* h, const uint8_t* env_mask_dev, void* mask_dev, void* stream);
 int zs_action_mask_bind(zs_handle* h, void* mask_dev_or_null);
 
+/* ---- per-env zombie counts and time limits (ZS_FLAG_ENV_PARAMS) ----------------------------------------
+ * A flagged handle holds, per env, the triple (initial_zombies, minimum_zombies, max_episode_steps) twice: the
+ * NEXT triple and the CURRENT one.  After zs_create both equal the config's values, and until the first
+ * zs_env_params_set the handle behaves exactly like one without the flag.  Every reset of env e (the implicit
+ * first one, zs_reset, an autoreset, alone or fused into the step launch) copies next -> current and then spawns
+ * initial_e zombies; until the env's next reset its zombie respawns (by the tick or by k_respawn) keep minimum_e
+ * zombies and its TimeLimit truncates at max_steps_e (0: none), read from the current triple.  So an episode has
+ * one difficulty from its first tick to its last.  The config's values are caps: 0 <= initial_e <=
+ * cfg.initial_zombies, 0 <= minimum_e <= cfg.minimum_zombies, max_steps_e >= 0; the entity slots, the step plan
+ * and the LDS images stay functions of the config alone.  New zombies go into the lowest free zombie slots, so an
+ * env with smaller counts is, slot for slot, the env of a handle configured with those counts.
+ *
+ * zs_env_params_set: two launches of one kernel (k_env_params) on `stream`, the first finding, in a scratch row
+ * of the handle, the entry that wins each env, the second storing the winners; entry k, k < n, writes the triple params_dev[k][0..2]
+ * into the next triple of env env_idx_dev[k] (NULL: env k).  Indices and values are device memory: nothing is
+ * read back, the host is not synchronised.  An entry whose env is outside [0, N) or whose values are outside
+ * the ranges above is not applied and raises the sticky ZS_OVF_PARAM_RANGE bit of zs_overflow's word; the other
+ * entries are applied.  When one env appears in several entries with different triples, one of the given
+ * triples wins whole (its three values are never mixed with another entry's); which one is not specified.
+ * n < 0 or n > 2^30: ZS_EINVAL; n == 0: nothing.  Like every call on a handle, set calls are serialised on the
+ * stream they are given: two of them in flight on different streams of one handle share the scratch row and may
+ * drop or mix entries.
+ * zs_env_params_check: *refused_host = 1 when ZS_OVF_PARAM_RANGE is up (everything queued on `stream` included),
+ * else 0, and clears that bit alone (the other ZS_OVF_* bits stay); synchronises the stream.
+ * zs_env_params_get: the next (which = 0) or current (which = 1) triples of all N envs into out_dev, int32
+ * [N][3], one launch on `stream`.  Any other `which`: ZS_EINVAL.
+ * All three: ZS_ESTATE on a handle created without ZS_FLAG_ENV_PARAMS.
+ * Snapshot records of a flagged handle carry both triples (zs_snapshot_layout's out[23]), and its fingerprint
+ * covers the flag: flagged and unflagged handles do not exchange records. */
+int zs_env_params_set(zs_handle* h, const int32_t* env_idx_dev, int32_t n, const int32_t* params_dev, void* stream);
+int zs_env_params_get(zs_handle* h, int32_t which, int32_t* out_dev, void* stream);
+int zs_env_params_check(zs_handle* h, uint32_t* refused_host, void* stream);
+
 /* Diagnostics (not part of the reference surface): when enabled, every k_tick
  * (the step kernel), k_obs (the observation kernel) and k_reset (world rebuild)
  * launch is bracketed by HIP events on its stream.  zs_profile_read synchronizes
@@ -419,7 +461,8 @@ int zs_profile_read(zs_handle* h, double out[8]);
  * and an unmasked zs_reset's observations ("step launch": the step writes them itself),
  * "obs_kernel_masked" that of a zs_reset / zs_observe with an env mask, "obs_encoders"
  * ("patched", "select" or "") the encoders of k_obs_ring; "mask_kernel", "mask_grid", "mask_block" the
- * action-mask launch (zs_action_mask) and "mask_bound" whether a buffer is bound.  Returns ZS_OK. */
+ * action-mask launch (zs_action_mask) and "mask_bound" whether a buffer is bound; "env_params" whether the handle
+ * carries per-env triples (ZS_FLAG_ENV_PARAMS).  Returns ZS_OK. */
 int zs_describe(zs_handle* h, char* buf, int32_t len);
 /* Diagnostics: out[0], out[1] = the two pending-reset list counts, out[2] = the deferred-respawn
  * count (after everything queued on stream), out[3] = the list parity the next step drains. */

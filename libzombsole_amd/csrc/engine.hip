@@ -9,7 +9,8 @@
 // behind the ABI; k_obs_state_pack / k_obs_state_unpack move the observation encoders' inputs between
 // handles as per-env records (zs_obs_state.hpp); k_action_mask (zs_mask.hpp, its own unit) writes the per-agent
 // action masks of the discrete tables, on request or as the last launch of every step; k_snapshot / k_restore / k_pending_list move complete envs in
-// and out of records (zs_snapshot.hpp) by the record walker of zs_record.hpp.
+// and out of records (zs_snapshot.hpp) by the record walker of zs_record.hpp; k_env_params (its own unit) scatters
+// per-env zombie counts and time limits into the envs' next triples (ZS_FLAG_ENV_PARAMS).
 //
 // Semantics follow the reference exactly (parity: tests/); every sqrt range
 // test of the reference is replaced by its exact integer d^2 equivalent.
@@ -404,7 +405,8 @@ __global__ __launch_bounds__(256) void k_obs_state_unpack(Dev d, ObsStateLayout 
 // staged in LDS so a lane can index it by section.
 // ---------------------------------------------------------------------------
 static_assert(ZS_SNAP_NSCAL == S_NSCAL && ZS_SNAP_RING == ZS_RING_WORDS, "zs_snapshot.hpp mirrors zs_device.hpp");
-static_assert(SNAP_NSEC <= REC_MAX_SEC, "a snapshot record's sections fit a table");
+static_assert(SNAP_NSEC + 1 <= REC_MAX_SEC, "a snapshot record's sections (with env_params) fit a table");
+static_assert(ZS_SNAP_ENVP == 2 * EP_N, "the env_params section is both triples");
 
 __device__ __forceinline__ void rec_stage_table(const RecTable& arg, RecTable* lds) {
     static_assert(sizeof(RecTable) % 4 == 0, "dword copy");
@@ -540,6 +542,7 @@ struct zs_handle {
     int* d_rcount;  // [2]
     int rpar = 0;
     uint64_t snap_fp = 0;  // snapshot_fingerprint() of the config (zs_snapshot.hpp)
+    int32_t* d_envp_owner = nullptr;  // ZS_FLAG_ENV_PARAMS: zs_env_params_set's scratch, int32 [N], -1 between calls
     void* mask_bound = nullptr;  // zs_action_mask_bind: every zs_step ends with a mask launch into it
     // the drop-ins' per-call path (zs_host_*), set up by its first call: one pinned, device-mapped input
     // block (actions, then the `random` state as rings + st words) the kernels read in place, one pinned,
@@ -833,7 +836,8 @@ static int create_env_arrays(zs_handle* h, const zs_map_desc& m) {
     TRY(dalloc(h, &d.present, E * N));
     TRY(dalloc(h, &d.serial, E * N));
     TRY(dalloc(h, &d.order, E * N));
-    TRY(dalloc(h, &d.scal, (size_t)S_NSCAL * N));
+    // ZS_FLAG_ENV_PARAMS: both triples behind the scalar rows, [6][N] (envp_cur(), envp_next(): zs_device.hpp)
+    TRY(dalloc(h, &d.scal, (size_t)(S_NSCAL + ((d.flags & ZS_FLAG_ENV_PARAMS) ? 2 * EP_N : 0)) * N));
     TRY(dalloc(h, &d.prev_life, (size_t)d.A * N));
     TRY(dalloc(h, &d.listed, (size_t)d.A * N));
     TRY(dalloc(h, &d.obst_hp, (size_t)d.O * N));
@@ -888,6 +892,9 @@ static int create_env_arrays(zs_handle* h, const zs_map_desc& m) {
         TRY(dalloc(h, &d.alog_n, N));
     }
     TRY(dalloc(h, &d.resp_count, 1));
+    if (d.flags & ZS_FLAG_ENV_PARAMS) {
+        TRY(dalloc(h, &h->d_envp_owner, N + 1));  // and, behind the row, zs_env_params_check's word
+    }
     return ZS_OK;
 }
 
@@ -916,6 +923,8 @@ static int create_step_plan(zs_handle* h) {
                              d.fobs ? d.obsl.bytes + 4 * d.obs_stat : 0};
     const StepPlan& p = h->step = step_plan(shape, h->ov);
     if (p.error) return fail(ZS_EINVAL, p.error);
+    if (!tick_lst_is_behind_misc(tick_layout(64 / p.G, d.E, d.DW, p.rw_cap, p.cand_cap, p.lists_cap, d.A), d.A))
+        return fail(ZS_ESTATE, "tick_layout(): the lst row is not behind the MISC rows (zs_tick.hpp LEADER_WORD)");
     d.rw_cap = p.rw_cap;
     d.rw_step = p.rw_step;
     d.cand_cap = p.cand_cap;
@@ -938,6 +947,8 @@ extern "C" int zs_create(const zs_config* cfg, int device, zs_handle** out) {
     *out = nullptr;
     int rc = validate(cfg);
     if (rc) return rc;
+    if ((cfg->flags & ZS_FLAG_ENV_PARAMS) && (cfg->flags & ZS_FLAG_VIEWER))  // nothing resets or steps a viewer's envs
+        return fail(ZS_ESTATE, "zs_create: ZS_FLAG_ENV_PARAMS: not on a viewer handle (ZS_FLAG_VIEWER)");
     HIPCHK(hipSetDevice(device));
     HandleOwner owner{new zs_handle()};
     zs_handle* h = owner.h;
@@ -1002,6 +1013,10 @@ extern "C" int zs_create(const zs_config* cfg, int device, zs_handle** out) {
     // every env starts "pending reset": the first zs_step (or zs_reset) builds its world
     hipLaunchKernelGGL(k_init_pending, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, 0, d, h->d_rlist[0],
                        h->d_rcount);
+    if (d.flags & ZS_FLAG_ENV_PARAMS) {  // both triples of every env start as the config's values
+        const hipError_t pe = launch_env_params_init(0, d, h->d_envp_owner);
+        if (pe != hipSuccess) return fail(ZS_EHIP, std::string("k_env_params_init: ") + hipGetErrorString(pe));
+    }
     // default seeds: env index (every env has a valid stream even if never seeded)
     std::vector<uint64_t> seeds(N);
     for (size_t i = 0; i < N; i++) seeds[i] = i;
@@ -1548,7 +1563,7 @@ extern "C" int zs_obs_state_unpack(zs_handle* h, const void* rec_dev, int32_t re
 // ---------------------------------------------------------------------------
 static SnapshotLayout handle_snapshot_layout(const zs_handle* h) {
     const Dev& d = h->d;
-    return snapshot_layout(d.E, d.O, d.DW, d.OW, d.A);
+    return snapshot_layout(d.E, d.O, d.DW, d.OW, d.A, (d.flags & ZS_FLAG_ENV_PARAMS) != 0);
 }
 
 // the engine-side table of a snapshot record (zs_record.hpp): the handle's arrays in record order
@@ -1557,7 +1572,7 @@ static RecTable snapshot_table(const zs_handle* h) {
     void* const base[SNAP_NSEC] = {d.ring, d.dead, d.obst_hp, d.obst_present, d.obst_nonpos, d.pos, d.life, d.serial,
                                    d.scal, d.hp_dirty, d.dead_dirty, d.rngst, d.prev_life,
                                    d.weapon, d.present, d.order, d.listed};
-    return snapshot_rec_table(base, d.E, d.O, d.DW, d.OW, d.A, (size_t)d.N);
+    return snapshot_rec_table(base, d.E, d.O, d.DW, d.OW, d.A, (size_t)d.N, (d.flags & ZS_FLAG_ENV_PARAMS) ? envp_cur(d) : nullptr);
 }
 
 extern "C" int zs_snapshot_layout(const zs_handle* h, int32_t out[24]) {
@@ -1571,6 +1586,7 @@ extern "C" int zs_snapshot_layout(const zs_handle* h, int32_t out[24]) {
     out[SNAP_NSEC + 3] = (int32_t)(uint32_t)(h->snap_fp >> 32);
     out[SNAP_NSEC + 4] = ZS_SNAP_NSCAL;
     out[SNAP_NSEC + 5] = ZS_SNAP_RING;
+    out[SNAP_NSEC + 6] = L.envp;
     return ZS_OK;
 }
 
@@ -1613,6 +1629,54 @@ extern "C" int zs_restore(zs_handle* h, const void* rec_dev, int32_t rec_bytes, 
     hipLaunchKernelGGL(k_pending_list, dim3((unsigned)std::min(64, (d.N + 255) / 256)), dim3(256), 0, s,
                        (const int32_t*)(d.scal + (size_t)S_NEEDRESET * d.N), d.N, h->d_rlist[p], h->d_rcount + p);
     HIPCHK(hipGetLastError());
+    return ZS_OK;
+}
+
+// ---------------------------------------------------------------------------
+// per-env zombie counts and time limits (ZS_FLAG_ENV_PARAMS; k_env_params.hip): asynchronous, nothing read back
+// ---------------------------------------------------------------------------
+static int env_params_refused(const zs_handle* h, const char* call) {
+    if (h->d.flags & ZS_FLAG_ENV_PARAMS) return ZS_OK;
+    return fail(ZS_ESTATE, std::string(call) + ": the handle was created without ZS_FLAG_ENV_PARAMS");
+}
+
+extern "C" int zs_env_params_set(zs_handle* h, const int32_t* env_idx_dev, int32_t n, const int32_t* params_dev, void* stream) {
+    if (!h) return fail(ZS_EINVAL, "null handle");
+    int rc = env_params_refused(h, "zs_env_params_set");
+    if (rc) return rc;
+    if (n < 0) return fail(ZS_EINVAL, "n must be >= 0");
+    if (n == 0) return ZS_OK;
+    if (n > (1 << 30)) return fail(ZS_EINVAL, "n must be <= 2^30");
+    if (!params_dev) return fail(ZS_EINVAL, "null argument");
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(launch_env_params_set(s, h->d, h->d_envp_owner, env_idx_dev, n, params_dev));
+    return ZS_OK;
+}
+
+extern "C" int zs_env_params_check(zs_handle* h, uint32_t* refused_host, void* stream) {
+    if (!h || !refused_host) return fail(ZS_EINVAL, "null argument");
+    int rc = env_params_refused(h, "zs_env_params_check");
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(hipSetDevice(h->device));
+    uint32_t* word = (uint32_t*)(h->d_envp_owner + h->d.N);
+    HIPCHK(launch_env_params_check(s, h->d, word));
+    uint32_t f = 0;
+    HIPCHK(hipMemcpyAsync(&f, word, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    *refused_host = (f & ZS_OVF_PARAM_RANGE) ? 1u : 0u;
+    return ZS_OK;
+}
+
+extern "C" int zs_env_params_get(zs_handle* h, int32_t which, int32_t* out_dev, void* stream) {
+    if (!h || !out_dev) return fail(ZS_EINVAL, "null argument");
+    int rc = env_params_refused(h, "zs_env_params_get");
+    if (rc) return rc;
+    if (which != 0 && which != 1) return fail(ZS_EINVAL, "which must be 0 (next) or 1 (current)");
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(launch_env_params_get(s, h->d, which, out_dev));
     return ZS_OK;
 }
 
@@ -1715,12 +1779,12 @@ extern "C" int zs_describe(zs_handle* h, char* buf, int32_t len) {
              "\"step_wgs_per_cu\": %d, \"rng_window\": %d, \"obs_kernel\": \"%s\", \"reset_side_stream\": %d, "
              "\"reset_lds\": %d, \"respawn\": \"%s\", \"tick_waves\": %d, \"rng_step\": %d, \"par_exec\": %d, "
              "\"obs_kernel_masked\": \"%s\", \"obs_encoders\": \"%s\", \"mask_kernel\": \"k_action_mask\", "
-             "\"mask_grid\": %u, \"mask_block\": %d, \"mask_bound\": %d}",
+             "\"mask_grid\": %u, \"mask_block\": %d, \"mask_bound\": %d, \"env_params\": %d}",
              d.N, d.E, p.G, p.fused ? "k_step" : "k_tick", p.lds, p.resident, p.rw_cap,
              d.fobs ? "step launch" : obs_kernel_name(kf.kind), h->reset_side,
              p.reset_lds, p.defer_respawn ? "k_respawn" : "tick", p.tick_waves, p.rw_step,
              d.par_exec, obs_kernel_name(h->obs.masked.kind), obs_encoders_name(kf), zs_mask_grid(d.N), ZS_MASK_BLOCK,
-             h->mask_bound ? 1 : 0);
+             h->mask_bound ? 1 : 0, (d.flags & ZS_FLAG_ENV_PARAMS) ? 1 : 0);
     return ZS_OK;
 }
 

@@ -149,6 +149,17 @@ struct Dev {
     uint32_t* ovf;
 };
 
+// ZS_FLAG_ENV_PARAMS (Dev::flags): per env (initial_zombies, minimum_zombies, max_episode_steps), [3][N] each: the
+// triple of the env's running episode (every reset copies next -> current; the respawn deficit and the TimeLimit read
+// it) and the triple its next reset takes up (zs_env_params_set writes it).  The Dev has no field for them, so the
+// kernel argument of every launch is what it is without the feature: a flagged handle's two arrays lie in the `scal`
+// allocation, behind its S_NSCAL rows (which stay the per-env scalars, and the snapshot record's scal section), current
+// first, so a record takes both as one [6][N] column section.  Without the flag nothing lies there, and the kernels
+// read the uniforms initial_zombies, minimum_zombies and max_steps.
+enum { EP_INITIAL = 0, EP_MINIMUM, EP_MAXSTEPS, EP_N };  // rows of envp_cur() / envp_next()
+__host__ __device__ __forceinline__ int32_t* envp_cur(const Dev& d) { return d.scal + (size_t)S_NSCAL * d.N; }
+__host__ __device__ __forceinline__ int32_t* envp_next(const Dev& d) { return d.scal + (size_t)(S_NSCAL + EP_N) * d.N; }
+
 // the launch's Dev (its first kernel argument, at kernarg offset 0) through a pointer the compiler cannot
 // see through, so the fields read after it are loaded where they are used instead of held in SGPRs across
 // the whole kernel (tick_wg, reset_env_wave, respawn_env_wave, k_obs_ring's encoders).

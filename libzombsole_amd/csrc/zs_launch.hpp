@@ -5,6 +5,7 @@
 //   k_obs_t.hip   once per observation dtype (-DZS_OBS_T=0/1/2): every observation kernel
 //   k_reset.hip   k_reset, k_respawn, k_list_filter
 //   k_mask.hip    k_action_mask (zs_mask.hpp)
+//   k_env_params.hip  k_env_params, k_env_params_get, k_env_params_init, k_env_params_check (ZS_FLAG_ENV_PARAMS)
 //   engine.hip    the C ABI and the small helper kernels (the launches are planned in zs_obs_plan.hpp, zs_step_plan.hpp)
 // Each unit exports plain host functions that launch its kernels; nothing but Dev, the observation
 // plan's ObsKernel (zs_obs_plan.hpp) and plain pointers crosses the units.
@@ -71,3 +72,11 @@ hipError_t stamps_reset(unsigned long long* wg, int clear);
 // action masks (zs_mask.hpp): uint8 [N][A][8] into out, 8-byte aligned, for the envs whose env_mask byte is
 // nonzero (null: all)
 hipError_t launch_action_mask(hipStream_t s, const Dev& d, const uint8_t* env_mask, void* out);
+
+// per-env zombie counts and time limits (k_env_params.hip; ZS_FLAG_ENV_PARAMS handles): entry k
+// < n of params ([n][3]) into the next triple of env idx[k] (null: k), two launches (owner: int32 [N] scratch, -1
+// between calls); the next or current triples of all envs as [N][3]; both triples = the config's, owner = -1
+hipError_t launch_env_params_set(hipStream_t s, const Dev& d, int32_t* owner, const int32_t* idx, int n, const int32_t* params);
+hipError_t launch_env_params_get(hipStream_t s, const Dev& d, int current, int32_t* out);
+hipError_t launch_env_params_init(hipStream_t s, const Dev& d, int32_t* owner);
+hipError_t launch_env_params_check(hipStream_t s, const Dev& d, uint32_t* out);  // *out = the range word; its PARAM_RANGE bit cleared

@@ -41,7 +41,7 @@ enum {
     REC_I16 = 1,    // int16 in the record, int32 in the engine: saturated when packed, sign-extended when restored
     REC_BYTE = 2,   // 1 byte in both
 };
-#define REC_MAX_SEC 17  // SNAP_NSEC (zs_snapshot.hpp), the longest record
+#define REC_MAX_SEC 18  // SNAP_NSEC + 1 (zs_snapshot.hpp): the longest record, a ZS_FLAG_ENV_PARAMS handle's
 
 // Entry nsec of every array stands for the padding (no base, REC_BYTE), so an index that rec_find returns is
 // always inside the arrays.  No section of a table is empty (rec_table leaves empty ones out): the byte after
@@ -229,14 +229,21 @@ ZS_HD inline void rec_copy_chunk(const RecTable& T, RecChunk* row, size_t e, int
 // The tables of the two record types, from the engine's arrays in record order (base[], of a handle of N envs).
 // ---------------------------------------------------------------------------
 // base: ring, dead, obst_hp, obst_present, obst_nonpos, pos, life, serial, scal, hp_dirty, dead_dirty, rngst,
-// prev_life, weapon, present, order, listed (SNAP_*)
-inline RecTable snapshot_rec_table(void* const base[SNAP_NSEC], int E, int O, int DW, int OW, int A, size_t N) {
+// prev_life, weapon, present, order, listed (SNAP_*); env_params: the [6][N] columns of a ZS_FLAG_ENV_PARAMS handle
+// (current triple, then next), whose record holds them between prev_life and the byte rows, else null
+inline RecTable snapshot_rec_table(void* const base[SNAP_NSEC], int E, int O, int DW, int OW, int A, size_t N,
+                                   void* env_params = nullptr) {
     const size_t rows[SNAP_NSEC] = {ZS_SNAP_RING, (size_t)DW, (size_t)O, (size_t)OW, (size_t)OW, (size_t)E, (size_t)E, (size_t)E,
                                     0, 0, 0, 0, 0, (size_t)E, (size_t)E, (size_t)E, 0};
-    RecSection sec[SNAP_NSEC];
-    for (int s = 0; s < SNAP_NSEC; s++) sec[s] = RecSection{base[s], rows[s], s < SNAP_NWORD ? REC_DWORD : REC_BYTE};
-    const SnapshotLayout L = snapshot_layout(E, O, DW, OW, A);
-    return rec_table(sec, L.off, SNAP_NSEC, L.rec_bytes, N);
+    const SnapshotLayout L = snapshot_layout(E, O, DW, OW, A, env_params != nullptr);
+    RecSection sec[SNAP_NSEC + 1];
+    int off[SNAP_NSEC + 2], n = 0;
+    for (int s = 0; s < SNAP_NSEC; s++) {
+        if (s == SNAP_NWORD && env_params) sec[n] = RecSection{env_params, 0, REC_DWORD}, off[n++] = L.envp;
+        sec[n] = RecSection{base[s], rows[s], s < SNAP_NWORD ? REC_DWORD : REC_BYTE}, off[n++] = L.off[s];
+    }
+    off[n] = L.off[SNAP_NSEC];
+    return rec_table(sec, off, n, L.rec_bytes, N);
 }
 
 // base: hp_dirty, dead_dirty, pos, life, dead, obst_present, obst_hp, weapon, present; L: obs_state_layout()

@@ -215,9 +215,17 @@ __device__ __forceinline__ void reset_env_wave(const Dev& d0, const ResetLds& L,
         if (wave_spawn(*dp, L, r, e, A, 0, dp->nps, n_order, serial) < A) rc = ZS_ENOSPACE;
     }
     RST(3); ZS_RST_RELOAD();
+    // ZS_FLAG_ENV_PARAMS: the env's next triple (lane k: value k) becomes its current one, whatever the reset's
+    // outcome; read here, where its first value is used, not held in a register across the players' spawns
+    int nzp = -1;  // (-1: the config's count, read below as before)
+    if (dp->flags & ZS_FLAG_ENV_PARAMS) {
+        const int v = envp_next(*dp)[(size_t)min(lane, EP_N - 1) * N + e];
+        if (lane < EP_N) envp_cur(*dp)[(size_t)lane * N + e] = v;
+        nzp = __shfl(v, EP_INITIAL);
+    }
     if (rc == ZS_OK) {
         // spawn_zombies(initial) (game.py:189-194): Zombie() draws randint(50, 100) first
-        int nz = dp->initial_zombies;
+        const int nz = nzp >= 0 ? nzp : dp->initial_zombies;
         for (int b0 = 0; b0 < nz; b0 += dp->E + 8) {  // randint(50, 100) = 50 + _randbelow(51) each
             int cnt = min(nz - b0, dp->E + 8);
             wave_draws(r, 51, 0, cnt, cnt, [&](int t, uint32_t v) { L.jbuf[t] = v; });
@@ -363,6 +371,10 @@ __device__ __forceinline__ void respawn_env_wave(const Dev& d0, const ResetLds& 
     wave_rng_fetch(r, rv);
     const uint32_t st_in = dp->rngst[e];
     const int n0 = dp->scal[S_NORDER * N + e], serial0 = dp->scal[S_SERIAL * N + e];
+    // the zombies to keep: the running episode's own count (ZS_FLAG_ENV_PARAMS), else the config's
+    // (-1: the config's, read where it is used)
+    int minz = -1;
+    if (dp->flags & ZS_FLAG_ENV_PARAMS) minz = envp_cur(*dp)[(size_t)EP_MINIMUM * N + e];
     const int sl = min(lane, E - 1);
     const int32_t vp = dp->pos[EIX(*dp, sl, e)], vl = dp->life[EIX(*dp, sl, e)];
     const uint8_t vw = dp->weapon[EIX(*dp, sl, e)], vr = dp->present[EIX(*dp, sl, e)], vo = dp->order[EIX(*dp, sl, e)];
@@ -427,7 +439,7 @@ __device__ __forceinline__ void respawn_env_wave(const Dev& d0, const ResetLds& 
     // Game.spawn_zombies(count): the deficit's Zombie()s go into the free zombie slots, lowest first
     int nz = 0;
     for (int b = Z0; b < E; b += 64) nz += __popcll(__ballot(b + lane < E && L.lpres[b + lane]));
-    const int k = max(dp->minimum_zombies - nz, 0);
+    const int k = max((minz >= 0 ? minz : dp->minimum_zombies) - nz, 0);
 #ifdef ZS_STAMPS
     if (lane == 0 && k > 0 && blockIdx.x < ZS_STAMP_WGS) g_stamp_wg[blockIdx.x * ZS_NPHASE + 19] += 1ull << 32;  // placing ones
 #endif

@@ -26,6 +26,8 @@
 //     dead_dirty   u32                  dead-body chunks that may be non-zero
 //     rngst        u32                  the MT19937 ring's offset, slot and ready bits
 //     prev_life    i32 [A]              the reward tracker's previous life per agent
+//   on a ZS_FLAG_ENV_PARAMS handle only:
+//     env_params   i32 [6]              the running episode's (initial, minimum, max_steps), then the next reset's
 //   the byte rows:
 //     weapon, present, order  u8 [E] each
 //     listed       u8 [A]               ([a][N] columns in the engine)
@@ -55,18 +57,27 @@ enum {
 };
 #define SNAP_NWORD SNAP_WEAPON   // sections [0, SNAP_NWORD) hold 4-byte elements, the rest bytes
 
+#define ZS_SNAP_ENVP 6   // words of the env_params section: the current triple, then the next one
+
 struct SnapshotLayout {
     int off[SNAP_NSEC + 1];  // byte offset of every section; off[SNAP_NSEC] = where the zero padding starts
     int rec_bytes;           // a multiple of 16
+    int envp;                // byte offset of the env_params section (ZS_FLAG_ENV_PARAMS handles), else 0
 };
 
-ZS_HD inline SnapshotLayout snapshot_layout(int E, int O, int DW, int OW, int A) {
+// env_params: the record of a ZS_FLAG_ENV_PARAMS handle, which holds one section more, env_params i32 [ZS_SNAP_ENVP]
+// (the engine's [6][N] columns), after prev_life, the last of the 4-byte sections, and before the byte rows
+ZS_HD inline SnapshotLayout snapshot_layout(int E, int O, int DW, int OW, int A, bool env_params = false) {
     const int bytes[SNAP_NSEC] = {4 * ZS_SNAP_RING, 4 * DW, 4 * O, 4 * OW, 4 * OW, 4 * E, 4 * E, 4 * E,
                                   4 * ZS_SNAP_NSCAL, 4, 4, 4, 4 * A,
                                   E, E, E, A};
     SnapshotLayout L;
+    L.envp = 0;
     int o = 0;
-    for (int s = 0; s < SNAP_NSEC; s++) L.off[s] = o, o += bytes[s];
+    for (int s = 0; s < SNAP_NSEC; s++) {
+        if (s == SNAP_NWORD && env_params) L.envp = o, o += 4 * ZS_SNAP_ENVP;
+        L.off[s] = o, o += bytes[s];
+    }
     L.off[SNAP_NSEC] = o;
     L.rec_bytes = (o + 15) & ~15;
     return L;
@@ -77,7 +88,9 @@ ZS_HD inline SnapshotLayout snapshot_layout(int E, int O, int DW, int OW, int A)
 // records.  Covered: W, H, O, E, A, P, Z, the rules, the reward mode, max_episode_steps, the initial and minimum
 // zombies, and the static tables: obstacle cells and kinds, player and zombie spawn lists, objective cells, agent
 // weapons, bot types (each with its length).  Deliberately not covered: the env count, the observation settings
-// (scope, encoding, width, dtype, agent codes), the flags, lanes_per_env and the launch overrides.
+// (scope, encoding, width, dtype, agent codes), lanes_per_env, the launch overrides and the flags, but for
+// ZS_FLAG_ENV_PARAMS: a handle with it has the longer record, so the flag is hashed in (last, and only when set: the
+// fingerprints of handles without it are what they were).
 // ---------------------------------------------------------------------------
 inline uint64_t snapshot_fp_add(uint64_t h, uint64_t v) {  // splitmix64's finaliser over the running value
     uint64_t z = (h ^ v) + 0x9E3779B97F4A7C15ull;
@@ -108,5 +121,6 @@ inline uint64_t snapshot_fingerprint(const zs_config* c) {
     h = snapshot_fp_table(h, m.objective_xy, 2 * m.n_objectives);
     h = snapshot_fp_table(h, c->agent_weapons, c->num_agents);
     h = snapshot_fp_table(h, c->bot_types, c->num_bots);
+    if (c->flags & ZS_FLAG_ENV_PARAMS) h = snapshot_fp_add(h, (uint64_t)ZS_FLAG_ENV_PARAMS);
     return h;
 }

@@ -103,6 +103,10 @@ ZS_HD inline TickLayout tick_layout(int ne, int E, int DW, int rw_cap, int cand_
     return L;
 }
 
+// the `lst` row (one word per env) lies right behind the MISC rows: the tick reads an env's entry as MISC row
+// MISC_N + 2A (zs_tick.hpp LEADER_WORD); zs_create refuses to run on a layout that says otherwise
+ZS_HD inline bool tick_lst_is_behind_misc(const TickLayout& L, int A) { return L.off_lst == L.off_misc + (MISC_N + 2 * A) * L.ne * 4; }
+
 // the reset work's image; its twist buffer doubles as the observation image of the env just rebuilt (obs_bytes)
 ZS_HD inline int reset_lds_bytes(int E, int DW, int ncand, int lists_cap, int obs_bytes = 0) {
     int o = DW * 4 + ncand * 4 + 2 * E * 4 + 4 * E + lists_cap * 4 + (E + 8) * 4;

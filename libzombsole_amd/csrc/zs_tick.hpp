@@ -1295,6 +1295,18 @@ __device__ __forceinline__ void env_cleanup_group(const Dev& d, Grp& c, bool run
     }
 }
 
+// What the leader reads of the zombie minimum and the time limit: one LDS word per env, staged with the other
+// per-env words at the stage-in (tick_wg) on every handle, from the config's uniforms or (ZS_FLAG_ENV_PARAMS) from
+// the env's current triple, so that the leader's part loads no Dev field and takes no branch for them: the zombies
+// to keep (the low bits; at most 254, zs_create's limit on the entity slots) and, in the top bit, whether this
+// step's TimeLimit strikes (max_steps > 0 and the episode's steps, this one included, reach it: both are known at
+// the stage-in).  The word is the env's entry of the `lst` row, which holds nothing for a stepping env until the
+// leader stores the env's stream state there at the end of its part.  tick_layout() puts that row right behind
+// the MISC rows (zs_create checks it: tick_lst_is_behind_misc), so it is MISC row MISC_N + 2A.
+#define LEADER_WORD(d, c) ((uint32_t)MISC(c, MISC_N + 2 * (d).A))
+#define LEADER_MIN_MASK 0x7fffffffu
+#define LEADER_TL_BIT 0x80000000u
+
 // the rest of the tick after the group's cleanup (leader)
 __device__ __forceinline__ void env_step_leader_b(const Dev& d, Grp& c, double* rew, uint8_t* done_out, uint8_t* trunc_out,
                                                   uint8_t* listed_out) {
@@ -1306,6 +1318,7 @@ __device__ __forceinline__ void env_step_leader_b(const Dev& d, Grp& c, double* 
     c.zd = MISC(c, MISC_ZD);
     c.odirty = 0;
     const int gfl = MISC(c, MISC_NMOVED);
+    const uint32_t lw = LEADER_WORD(d, c);  // read with the rows above: one LDS round for all of them
     const int nz = gfl & 0xffff, pa = (gfl >> 16) & 1, aa = (gfl >> 17) & 1, off = (gfl >> 18) & 1;
     SUB(3);
     // reward_tracker.update (gym/reward.py:30-35, 77-86)
@@ -1328,12 +1341,14 @@ __device__ __forceinline__ void env_step_leader_b(const Dev& d, Grp& c, double* 
     // alive", which only needs to know whether one more zombie gets placed (a free spawn cell).
     int za0 = 0, spawned = 0;
     c.respawn = 0;
-    if (nz < d.minimum_zombies) {
+    // the zombies to keep (the config's count or the running episode's own: LEADER_WORD)
+    const int minz = (int)(lw & LEADER_MIN_MASK);
+    if (nz < minz) {
         if (d.defer_respawn) {
             c.respawn = 1;
             if (nz == 0 && d.rules == ZS_RULES_EXTERMINATION) za0 = any_free_spawn(d, c);
         } else {
-            spawn_zombies(d, c, d.minimum_zombies - nz);
+            spawn_zombies(d, c, minz - nz);
             spawned = 1;
         }
     }
@@ -1372,7 +1387,7 @@ __device__ __forceinline__ void env_step_leader_b(const Dev& d, Grp& c, double* 
         for (int a = 0; a < A; a++) MISC(c, MISC_N + a) = LL(c, a);
     c.prevzd = c.zd;
     c.epsteps++;
-    if (d.max_steps > 0 && c.epsteps >= d.max_steps) tr = 1;
+    if (lw & LEADER_TL_BIT) tr = 1;  // the TimeLimit: max_steps > 0 && c.epsteps >= max_steps
     done_out[c.e] = (uint8_t)ended;
     trunc_out[c.e] = (uint8_t)tr;
     c.fin = ended || tr;
@@ -1566,6 +1581,7 @@ __device__ __forceinline__ void tick_wg(const Dev& d0, int wg, const int32_t* ac
         return min(dp->rw_step, maxw);
     };
     const int nmisc = MISC_N + 2 * A;
+    int pmin = 0, pmax = 0;  // the leader's word (second load round)
     if (active) {
         if (dp->pol_n) {
             pseed = dp->seeds[e];
@@ -1659,6 +1675,19 @@ __device__ __forceinline__ void tick_wg(const Dev& d0, int wg, const int32_t* ac
         }
         // the rest of the per-env scalars and reward tracker / env.agents rows (more rows than lanes)
         for (int f = j + G; f < nmisc; f += G) MISC(c, f) = misc_load(*dp, f, e);
+        // the zombies to keep and the time limit of the running episode, for the leader's word (LEADER_WORD below):
+        // the config's two uniforms, read here where the Dev is live, or (ZS_FLAG_ENV_PARAMS: a branch uniform over
+        // the launch) the env's own, loaded by its leader with the stage-in's second round (the RNG window's, which
+        // waits for the stream state of the first)
+        if (dp->flags & ZS_FLAG_ENV_PARAMS) {
+            if (leader) {
+                pmin = envp_cur(*dp)[(size_t)EP_MINIMUM * N + e];
+                pmax = envp_cur(*dp)[(size_t)EP_MAXSTEPS * N + e];
+            }
+        } else {
+            pmin = dp->minimum_zombies;
+            pmax = dp->max_steps;
+        }
         // RNG window: the next words of this env's stream, tempered
         uint32_t off, slot, ready;
         int b0 = j;
@@ -1692,6 +1721,8 @@ __device__ __forceinline__ void tick_wg(const Dev& d0, int wg, const int32_t* ac
     }
     wave_sync();
     if (stepping) {
+        // the leader's word: the episode's step count is in its MISC row now (staged by another lane of the env)
+        if (leader) lst[g] = ((uint32_t)pmin & LEADER_MIN_MASK) | (pmax > 0 && MISC(c, MISC_EPSTEPS) + 1 >= pmax ? LEADER_TL_BIT : 0u);
         // dict-order ranks for closest() tie-breaks
         for (int k = j; k < n_order; k += G) LR(c, LO(c, k)) = (uint8_t)k;
         // the cells of obstacles this env has lost (cleaned up, core.py:121-138) are free

@@ -18,7 +18,8 @@ SYMBOLS = ["zs_last_error", "zs_create", "zs_destroy", "zs_obs_shape", "zs_seed"
            "zs_host_layout", "zs_host_step", "zs_host_reset", "zs_host_observe",
            "zs_obs_state_layout", "zs_obs_state_pack", "zs_obs_state_unpack",
            "zs_snapshot_layout", "zs_snapshot", "zs_restore",
-           "zs_action_mask", "zs_action_mask_bind"]
+           "zs_action_mask", "zs_action_mask_bind",
+           "zs_env_params_set", "zs_env_params_get", "zs_env_params_check"]
 
 _lib = None
 
@@ -81,6 +82,9 @@ def load_library(path=None):
     L.zs_restore.argtypes = [vp, vp, i32, i32, vp, vp, i32, vp]
     L.zs_action_mask.argtypes = [vp, vp, vp, vp]
     L.zs_action_mask_bind.argtypes = [vp, vp]
+    L.zs_env_params_set.argtypes = [vp, vp, i32, vp, vp]
+    L.zs_env_params_get.argtypes = [vp, i32, vp, vp]
+    L.zs_env_params_check.argtypes = [vp, C.POINTER(C.c_uint32), vp]
     for s in SYMBOLS:
         if s != "zs_last_error":
             getattr(L, s).restype = C.c_int
@@ -354,6 +358,8 @@ class Engine(object):
             v = [int(x) for x in out]
             L = dict(zip(("rec_bytes",) + _abi.SNAPSHOT_SECTIONS + ("pad",), v))
             L["fingerprint"] = (v[19] & 0xffffffff) | ((v[20] & 0xffffffff) << 32)
+            if v[23]:  # a FLAG_ENV_PARAMS handle's record: the current triple, then the next one
+                L["env_params"] = v[23]
             self._snl = L
         return self._snl
 
@@ -412,6 +418,65 @@ class Engine(object):
         rc = self.L.zs_restore(self.h, _ptr(rec), int(rec.shape[1]), int(rec.shape[0]), _ptr(s), _ptr(d), n, self._stream())
         if rc:
             _raise(self.L, rc, "zs_restore")
+
+    # -- per-env zombie counts and time limits (zs_env_params_*; a config with FLAG_ENV_PARAMS) -------------------
+    def set_env_params(self, params, envs=None, check=True):
+        """The triples (initial_zombies, minimum_zombies, max_episode_steps) that `envs` (an index tensor or
+        sequence; default: envs 0..n-1) take up at their next reset (zs_env_params_set); a running episode keeps
+        its own.  params: int32 [n, 3], or a dict of three [n] tensors under those names.  The config's counts are
+        caps and max_episode_steps >= 0 (0: none); an entry outside them, or naming an env outside [0, N), is not
+        applied.  When an env is named more than once, one of its triples wins whole.  check=True calls
+        zs_env_params_check afterwards (one synchronisation: it reads OVF_PARAM_RANGE and clears that bit alone) and
+        raises ValueError if an entry was refused; check=False never synchronises: the refusal stays in overflow() as OVF_PARAM_RANGE."""
+        t = self.torch
+        if isinstance(params, dict):
+            params = t.stack([t.as_tensor(params[k]).to(self.device).reshape(-1) for k in _abi.ENV_PARAMS], dim=1)
+        p = t.as_tensor(params)
+        if p.dim() != 2 or p.shape[1] != 3 or p.dtype in (t.bool, t.float16, t.float32, t.float64):
+            raise ValueError("set_env_params: params are an integer tensor [n, 3] or a dict of %s" % (_abi.ENV_PARAMS,))
+        p = self._as_int32(p)
+        idx = envs
+        if idx is not None:
+            idx = t.as_tensor(idx)
+            if idx.dim() != 1 or idx.dtype in (t.bool, t.float16, t.float32, t.float64):
+                raise ValueError("set_env_params: envs is a 1-D integer tensor or sequence")
+            idx = self._as_int32(idx)
+        if idx is not None and idx.shape[0] != p.shape[0]:
+            raise ValueError("set_env_params: %d envs for %d triples" % (idx.shape[0], p.shape[0]))
+        rc = self.L.zs_env_params_set(self.h, _ptr(idx), int(p.shape[0]), _ptr(p), self._stream())
+        if rc:
+            _raise(self.L, rc, "zs_env_params_set")
+        if not check:
+            return
+        refused = C.c_uint32(0)  # reads OVF_PARAM_RANGE and clears that bit alone (one synchronisation)
+        rc = self.L.zs_env_params_check(self.h, C.byref(refused), self._stream())
+        if rc:
+            _raise(self.L, rc, "zs_env_params_check")
+        if refused.value:
+            raise ValueError("set_env_params: an env outside [0, %d) or a value outside its range (caps: the "
+                             "config's counts; max_episode_steps >= 0); the other entries were applied" % self.N)
+
+    def _as_int32(self, x):
+        """An integer tensor as a contiguous int32 device tensor; a value int32 does not hold becomes -1 (no env, no
+        count and no limit is -1: the device refuses the entry) instead of wrapping into range.  No synchronisation."""
+        t = self.torch
+        x = x.to(self.device)
+        if x.dtype != t.int32:
+            x = x.to(t.int64)
+            x = t.where((x < -2 ** 31) | (x > 2 ** 31 - 1), t.full_like(x, -1), x)
+        return x.to(t.int32).contiguous()
+
+    def env_params(self, current=False, out=None):
+        """int32 [N, 3]: every env's (initial_zombies, minimum_zombies, max_episode_steps), the triple its next
+        reset takes up, or with current=True the triple of its running episode (zs_env_params_get)."""
+        t = self.torch
+        o = t.empty((self.N, 3), dtype=t.int32, device=self.device) if out is None else out
+        if o.dtype != t.int32 or tuple(o.shape) != (self.N, 3) or not o.is_contiguous() or o.device != self.device:
+            raise ValueError("env_params: out is a contiguous int32 tensor [%d, 3] on %s" % (self.N, self.device))
+        rc = self.L.zs_env_params_get(self.h, 1 if current else 0, _ptr(o), self._stream())
+        if rc:
+            _raise(self.L, rc, "zs_env_params_get")
+        return o
 
     def gen_actions(self, step, n_discrete, out=None):
         o = self.actions if out is None else out
@@ -553,7 +618,7 @@ class Engine(object):
 
 
     def overflow(self, clear=False):
-        """Sticky range flags (_abi.OVF_INT16 | OVF_INT32) of every env since creation / the last clear."""
+        """Sticky range flags (_abi.OVF_INT16 | OVF_INT32 | OVF_PARAM_RANGE) of every env since creation / the last clear."""
         f = C.c_uint32(0)
         rc = self.L.zs_overflow(self.h, C.byref(f), 1 if clear else 0, self._stream())
         if rc:

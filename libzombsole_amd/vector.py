@@ -67,17 +67,19 @@ class BatchedZombsole(object):
                  observation_scope="world", observation_position_encoding="simple", agent_weapon="rifle",
                  observation_surroundings_width=21, observation_position_encoding_style="channels",
                  agent_weapons="rifle", obs_dtype=None, autoreset=True, device=None, lanes_per_env=0,
-                 action_masks=False):
+                 action_masks=False, env_params=False):
         if surface == "single":
             b = _abi.single_env_config(num_envs, rules_name, player_names, map_name, agent_id, initial_zombies,
                                        minimum_zombies, observation_scope, observation_position_encoding,
                                        agent_weapon, max_episode_steps,
-                                       _abi.DTYPE_I32 if obs_dtype is None else obs_dtype, autoreset, lanes_per_env)
+                                       _abi.DTYPE_I32 if obs_dtype is None else obs_dtype, autoreset, lanes_per_env,
+                                       env_params=env_params)
         elif surface == "multi":
             b = _abi.multi_env_config(num_envs, rules_name, player_names, map_name, agent_ids, initial_zombies,
                                       minimum_zombies, observation_surroundings_width,
                                       observation_position_encoding_style, agent_weapons, max_episode_steps,
-                                      _abi.DTYPE_I64 if obs_dtype is None else obs_dtype, autoreset, lanes_per_env)
+                                      _abi.DTYPE_I64 if obs_dtype is None else obs_dtype, autoreset, lanes_per_env,
+                                      env_params=env_params)
         else:
             raise ValueError("surface must be 'single' or 'multi'")
         self.surface = surface
@@ -101,6 +103,23 @@ class BatchedZombsole(object):
         Valid after every reset, step, restore / clone and load_checkpoint.  None without action_masks=True."""
         m = self.engine.masks
         return None if m is None else m[:, :, :self.engine.n_discrete]
+
+    # -- per-env difficulty (env_params=True): zombie counts and time limit per env, set on the device --------------
+    def set_env_params(self, params, envs=None, check=True):
+        """(initial_zombies, minimum_zombies, max_episode_steps) per env, taken up at each env's next reset
+        (Engine.set_env_params): int32 [n, 3] or a dict of three [n] tensors, for `envs` (default 0..n-1).  The
+        constructor's counts are the caps.  check=False never synchronises."""
+        self.engine.set_env_params(params, envs, check)
+
+    @property
+    def env_params(self):
+        """int32 [N, 3]: the triple every env takes up at its next reset."""
+        return self.engine.env_params()
+
+    @property
+    def env_params_current(self):
+        """int32 [N, 3]: the triple of every env's running episode."""
+        return self.engine.env_params(current=True)
 
     @property
     def obs(self):
