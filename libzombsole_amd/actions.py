@@ -108,7 +108,7 @@ _M64 = (1 << 64) - 1
 
 
 def splitmix64(x):
-    """splitmix64 finaliser (same constants as zs_gen_actions in engine.hip)."""
+    """splitmix64 finaliser (same constants as zs_gen_actions' kernel, k_gen_actions in csrc/k_state.hip)."""
     x = (x + 0x9E3779B97F4A7C15) & _M64
     z = x
     z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64

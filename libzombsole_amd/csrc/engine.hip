@@ -1,16 +1,14 @@
-// engine.hip — MI355X-native batched zombsole step engine (gfx950) and its C ABI.
+// engine.hip — the handle and the C ABI of the MI355X-native batched zombsole step engine (gfx950): host code only.
 //
-// A step (zs_step) is: k_reset (zs_reset.hpp, one wave per env that ended at the previous step, on
-// a side stream concurrent with the tick, or fused with it into k_step), k_tick (zs_tick.hpp, 64/G
-// envs per wave with G lanes per env and the env's hot state in LDS), k_respawn (deferred zombie
-// respawns, one wave per env) and the observation kernel (zs_obs.hpp: k_obs_ring / k_obs_pipe
-// persistent store streams, k_obs_gather for large maps, k_obs in general).  zs_step_graph replays
-// a step as a hipGraph.  k_seed / k_gen_actions / k_get_state / k_set_state are the small helpers
-// behind the ABI; k_obs_state_pack / k_obs_state_unpack move the observation encoders' inputs between
-// handles as per-env records (zs_obs_state.hpp); k_action_mask (zs_mask.hpp, its own unit) writes the per-agent
-// action masks of the discrete tables, on request or as the last launch of every step; k_snapshot / k_restore / k_pending_list move complete envs in
-// and out of records (zs_snapshot.hpp) by the record walker of zs_record.hpp; k_env_params (its own unit) scatters
-// per-env zombie counts and time limits into the envs' next triples (ZS_FLAG_ENV_PARAMS).
+// The kernels live in their own units behind plain launchers (zs_launch.hpp).  A step (zs_step) is: k_reset
+// (zs_reset.hpp, one wave per env that ended at the previous step, on a side stream concurrent with the tick, or
+// fused with it into k_step), k_tick (zs_tick.hpp, 64/G envs per wave with G lanes per env and the env's hot state
+// in LDS), k_respawn (deferred zombie respawns, one wave per env) and the observation kernel (zs_obs.hpp: k_obs_ring /
+// k_obs_pipe persistent store streams, k_obs_gather for large maps, k_obs in general), else k_tail, then k_action_mask
+// (zs_mask.hpp) when a mask buffer is bound.  zs_step_graph replays a step as a hipGraph.  The small helpers behind the
+// ABI (seeding, the policy stream, the state views, the drop-ins' per-call records) are k_state.hip's; the per-env
+// record movers (observation-state records, zs_obs_state.hpp; snapshot records, zs_snapshot.hpp and zs_record.hpp) are
+// k_records.hip's; k_env_params.hip scatters per-env zombie counts and time limits (ZS_FLAG_ENV_PARAMS).
 //
 // Semantics follow the reference exactly (parity: tests/); every sqrt range
 // test of the reference is replaced by its exact integer d^2 equivalent.
@@ -22,464 +20,11 @@
 #include <string>
 #include <vector>
 
-#include "zs_device.hpp"
-
-#include "zs_launch.hpp"
-#include "zs_reset.hpp"
-#include "zs_obs.hpp"
+#include "zs_launch.hpp"  // zs_device.hpp (Dev), the plans (zs_obs_plan.hpp, zs_step_plan.hpp)
 #include "zs_obs_state.hpp"
 #include "zs_snapshot.hpp"
 #include "zs_record.hpp"
-#include "zs_mask.hpp"
-
-// ---------------------------------------------------------------------------
-// seeding: random.seed(int) (init_by_array over abs(n) in 32-bit little-endian words)
-// ---------------------------------------------------------------------------
-__global__ void k_seed(Dev d, int env0, int n, const uint64_t* seeds) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    int e = env0 + i;
-    uint64_t sd = seeds[i];
-    d.seeds[e] = sd;
-    uint32_t* mt = d.ring + (size_t)e * ZS_RING_WORDS;
-    uint32_t key[2] = {(uint32_t)sd, (uint32_t)(sd >> 32)};
-    int klen = (sd >> 32) ? 2 : 1;
-    mt[0] = 19650218u;
-    for (int k = 1; k < ZS_MT_N; k++) mt[k] = 1812433253u * (mt[k - 1] ^ (mt[k - 1] >> 30)) + (uint32_t)k;
-    int a = 1, b = 0;
-    for (int k = (ZS_MT_N > klen ? ZS_MT_N : klen); k; k--) {
-        mt[a] = (mt[a] ^ ((mt[a - 1] ^ (mt[a - 1] >> 30)) * 1664525u)) + key[b] + (uint32_t)b;
-        a++;
-        b++;
-        if (a >= ZS_MT_N) {
-            mt[0] = mt[ZS_MT_N - 1];
-            a = 1;
-        }
-        if (b >= klen) b = 0;
-    }
-    for (int k = ZS_MT_N - 1; k; k--) {
-        mt[a] = (mt[a] ^ ((mt[a - 1] ^ (mt[a - 1] >> 30)) * 1566083941u)) - (uint32_t)a;
-        a++;
-        if (a >= ZS_MT_N) {
-            mt[0] = mt[ZS_MT_N - 1];
-            a = 1;
-        }
-    }
-    mt[0] = 0x80000000u;
-    // the seeded state is x[0..623]; the first draw twists, so the output stream starts at x[624]
-    mt_twist_serial(mt + ZS_MT_N, mt);  // block 1 -> slot 1 (current)
-    mt_twist_serial(mt, mt + ZS_MT_N);  // block 2 -> slot 0 (next, ready)
-    d.rngst[e] = 0u | (1u << 10) | (1u << 11);
-}
-
-// ---------------------------------------------------------------------------
-// bench / parity action stream (libzombsole_amd/actions.py; policy_action in zs_device.hpp)
-// ---------------------------------------------------------------------------
-// one thread per (env, agent): its triple
-__global__ void k_gen_actions(Dev d, uint64_t step, int n_discrete, int32_t* act) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= d.N * d.A) return;
-    const int e = i / d.A;
-    const int id = policy_id(d.seeds[e], step, n_discrete, i - e * d.A);
-    act[(size_t)i * 3 + 0] = c_discrete[id][0];
-    act[(size_t)i * 3 + 1] = c_discrete[id][1];
-    act[(size_t)i * 3 + 2] = c_discrete[id][2];
-}
-
-// The same policy for the step number in device memory (zs_step_graph with the reset work on a side
-// stream: launched after the reset fork, it gives the reset work a head start on the tick)
-__global__ void k_gen_actions_ctr(Dev d, const uint64_t* ctr, int n_discrete, int32_t* act) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= d.N * d.A) return;
-    const int e = i / d.A;
-    const int id = policy_id(d.seeds[e], ctr[0], n_discrete, i - e * d.A);
-    act[(size_t)i * 3 + 0] = c_discrete[id][0];
-    act[(size_t)i * 3 + 1] = c_discrete[id][1];
-    act[(size_t)i * 3 + 2] = c_discrete[id][2];
-}
-
-// the step's tail when no observation launch ends the step (observations written by the step launch)
-__global__ void k_tail(Dev d) {
-    if (threadIdx.x == 0) step_tail(d);
-}
-
-// ---------------------------------------------------------------------------
-// state views (one env, one thread; test pokes)
-// ---------------------------------------------------------------------------
-// env e's state record (layout: include/zombsole_mi355x.h), written by threads tid = 0..nt-1 of one workgroup
-// (every thread of the workgroup calls it)
-__device__ void state_record(const Dev& d, int e, int32_t* b, int tid, int nt) {
-    const int N = d.N, E = d.E;
-    __shared__ int nz;  // present zombies
-    if (tid == 0) nz = 0;
-    __syncthreads();
-    for (int s = d.A + d.P + tid; s < E; s += nt)
-        if (d.present[EIX(d, s, e)]) atomicAdd(&nz, 1);
-    __syncthreads();
-    if (tid == 0) {
-        b[0] = d.scal[S_T * N + e];
-        b[1] = d.scal[S_DEATHS * N + e];
-        b[2] = d.scal[S_ZD * N + e];
-        b[3] = d.scal[S_EPSTEPS * N + e];
-        b[4] = d.scal[S_NORDER * N + e];
-        b[5] = d.scal[S_NEEDRESET * N + e];
-        b[6] = E;
-        b[7] = d.O;
-        b[8] = d.W;
-        b[9] = d.H;
-        b[10] = d.scal[S_PREVZD * N + e];
-        b[11] = nz;
-        b[12] = d.scal[S_SERIAL * N + e];
-        b[13] = b[14] = b[15] = 0;
-    }
-    int32_t* r = b + ZS_STATE_HEADER;
-    for (int s = tid; s < E; s += nt) {
-        int32_t* q = r + s * ZS_STATE_ENTITY_WORDS;
-        int32_t p = d.pos[EIX(d, s, e)];
-        q[0] = s < d.A ? ZS_THING_AGENT : (s < d.A + d.P ? ZS_THING_PLAYER : ZS_THING_ZOMBIE);
-        q[1] = d.present[EIX(d, s, e)];
-        q[2] = unpack_x(p);
-        q[3] = unpack_y(p);
-        q[4] = d.life[EIX(d, s, e)];
-        q[5] = d.weapon[EIX(d, s, e)];
-        q[6] = s < d.A ? s : (s < d.A + d.P ? s - d.A : 0);
-        q[7] = (int32_t)d.serial[EIX(d, s, e)];
-    }
-    r += ZS_STATE_ENTITY_WORDS * E;
-    for (int s = tid; s < E; s += nt) r[s] = d.order[EIX(d, s, e)];
-    r += E;
-    for (int o = tid; o < d.O; o += nt) r[o] = d.obst_hp[(size_t)e * d.O + o];
-    r += d.O;
-    for (int o = tid; o < d.O; o += nt) r[o] = (d.obst_present[(size_t)e * d.OW + (o >> 5)] >> (o & 31)) & 1u;
-    r += d.O;
-    for (int a = tid; a < d.A; a += nt) r[a] = d.prev_life[(size_t)a * N + e];
-    r += d.A;
-    for (int a = tid; a < d.A; a += nt) r[a] = d.listed[(size_t)a * N + e];
-    r += d.A;
-    for (int w = tid; w < d.DW; w += nt) r[w] = (int32_t)d.dead[(size_t)e * d.DW + w];
-}
-
-__global__ void k_get_state(Dev d, int e, int32_t* buf) { state_record(d, e, buf, threadIdx.x, blockDim.x); }
-
-// ---------------------------------------------------------------------------
-// the drop-ins' per-call path (zs_host_step / zs_host_reset / zs_host_observe): one workgroup per env
-// ---------------------------------------------------------------------------
-// the process-global `random` state moved in (rings[e]: the getstate() block and its successor, st[e])
-// (host memory read in place: one round of 16-B loads, 1 248 words = 312 per env)
-__global__ void k_host_unpack(Dev d, const uint32_t* rings, const uint32_t* st, int* err) {
-    const int e = blockIdx.x, t = threadIdx.x;
-    if (e == 0 && t == 0) *err = 0;  // the call's error word starts clear (host_call; no memset launch)
-    static_assert(ZS_RING_WORDS % 4 == 0, "16-B copies");
-    const uint4* src = (const uint4*)(rings + (size_t)e * ZS_RING_WORDS);
-    uint4* dst = (uint4*)(d.ring + (size_t)e * ZS_RING_WORDS);
-    const int n4 = ZS_RING_WORDS / 4;  // 312: two per thread at most (blockDim 256)
-    uint4 a = t < n4 ? src[t] : uint4{}, b = t + 256 < n4 ? src[t + 256] : uint4{};
-    const uint32_t sv = t == 0 ? st[e] : 0u;
-    if (t < n4) dst[t] = a;
-    if (t + 256 < n4) dst[t + 256] = b;
-    if (t == 0) d.rngst[e] = sv;
-}
-
-// Word offsets of a host record's sections (ZS_HOST_* in include/zombsole_mi355x.h, zs_host_layout)
-struct HostLayout {
-    int words, rew, alog, dlog, state, obs, obs_bytes, R;
-};
-
-// everything a call returns to the host, for env e: outputs, RNG stream, logs, state record, observation
-__global__ void k_host_pack(Dev d, HostLayout L, const uint8_t* obs, const double* rew, const uint8_t* done,
-                            const uint8_t* trunc, const uint8_t* rst, int* err, int32_t* rec) {
-    const int e = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
-    int32_t* r = rec + (size_t)e * L.words;
-    const uint32_t st = d.rngst[e];
-    if (tid == 0) {
-        r[ZS_HOST_FLAGS] = (done[e] ? 1 : 0) | (trunc[e] ? 2 : 0) | (rst && rst[e] ? 4 : 0);
-        // every env's record carries the call's error word; host_call clears it ahead of the call's launches
-        // (not here: a block that cleared it would hide it from the blocks that read after it)
-        r[ZS_HOST_ERR] = *err;
-        r[ZS_HOST_ALOG_N] = d.alog ? d.alog_n[e] : 0;
-        r[ZS_HOST_DLOG_N] = d.dlog ? d.dlog_n[e] : 0;
-        r[ZS_HOST_RNG + ZS_MT_N] = (int32_t)(st & 1023u);
-    }
-    const uint32_t* blk = d.ring + (size_t)e * ZS_RING_WORDS + ((st >> 10) & 1u) * ZS_MT_N;
-    for (int k = tid; k < ZS_MT_N; k += nt) r[ZS_HOST_RNG + k] = (int32_t)blk[k];
-    const int32_t* rw = (const int32_t*)(rew + (size_t)e * L.R);
-    for (int k = tid; k < 2 * L.R; k += nt) r[L.rew + k] = rw[k];
-    if (d.alog)
-        for (int k = tid; k < 2 * d.E; k += nt) r[L.alog + k] = d.alog[(size_t)e * d.E * 2 + k];
-    if (d.dlog)
-        for (int k = tid; k < 5 * d.E; k += nt) r[L.dlog + k] = d.dlog[(size_t)e * d.E * 5 + k];
-    state_record(d, e, r + L.state, tid, nt);
-    // the observation: 16-B copies when the env's block allows (L.obs is 16-B aligned), else 2-B ones
-    const uint8_t* src = obs + (size_t)e * L.obs_bytes;
-    uint8_t* dst = (uint8_t*)(r + L.obs);
-    if (L.obs_bytes % 16 == 0 && ((size_t)e * L.obs_bytes) % 16 == 0 && (L.words % 4) == 0) {
-        for (int k = tid; k < L.obs_bytes / 16; k += nt) ((uint4*)dst)[k] = ((const uint4*)src)[k];
-    } else {
-        for (int k = tid; k < L.obs_bytes / 2; k += nt) ((uint16_t*)dst)[k] = ((const uint16_t*)src)[k];
-    }
-}
-
-__global__ void k_set_state(Dev d, int e, const int32_t* buf, int* err) {
-    if (threadIdx.x != 0) return;
-    const int N = d.N, E = d.E;
-    const int32_t* b = buf;
-    // needs_reset (b[5]) is the engine's own: pending resets are its work lists (an env on a list with
-    // the flag cleared would be reset and ticked by one call, one off the lists with the flag set would
-    // report a reset without a rebuild), so a record that disagrees is refused, nothing written
-    if (b[5] != d.scal[S_NEEDRESET * N + e]) {
-        *err = ZS_EINVAL;
-        return;
-    }
-    d.scal[S_T * N + e] = b[0];
-    d.scal[S_DEATHS * N + e] = b[1];
-    d.scal[S_ZD * N + e] = b[2];
-    d.scal[S_EPSTEPS * N + e] = b[3];
-    d.scal[S_NORDER * N + e] = b[4];
-    d.scal[S_PREVZD * N + e] = b[10];
-    d.scal[S_SERIAL * N + e] = b[12];
-    const int32_t* r = b + ZS_STATE_HEADER;
-    for (int s = 0; s < E; s++, r += ZS_STATE_ENTITY_WORDS) {
-        d.present[EIX(d, s, e)] = (uint8_t)r[1];
-        d.pos[EIX(d, s, e)] = pack_xy(r[2], r[3]);
-        d.life[EIX(d, s, e)] = r[4];
-        d.weapon[EIX(d, s, e)] = (uint8_t)r[5];
-        d.serial[EIX(d, s, e)] = (uint32_t)r[7];
-    }
-    for (int s = 0; s < E; s++) d.order[EIX(d, s, e)] = (uint8_t)*r++;
-    int any_nonpos = 0;
-    for (int o = 0; o < d.O; o++) {
-        int v = *r++;
-        d.obst_hp[(size_t)e * d.O + o] = hp_store_value(d, v);
-        d.hp_dirty[e] = 0xffffffffu;
-        uint32_t* w = &d.obst_nonpos[(size_t)e * d.OW + (o >> 5)];
-        *w = v <= 0 ? (*w | (1u << (o & 31))) : (*w & ~(1u << (o & 31)));
-        any_nonpos |= v <= 0;
-    }
-    for (int o = 0; o < d.O; o++) {
-        uint32_t* w = &d.obst_present[(size_t)e * d.OW + (o >> 5)];
-        *w = *r++ ? (*w | (1u << (o & 31))) : (*w & ~(1u << (o & 31)));
-    }
-    d.scal[S_ODIRTY * N + e] = any_nonpos;
-    for (int a = 0; a < d.A; a++) d.prev_life[(size_t)a * N + e] = *r++;
-    for (int a = 0; a < d.A; a++) d.listed[(size_t)a * N + e] = (uint8_t)*r++;
-    for (int w = 0; w < d.DW; w++) d.dead[(size_t)e * d.DW + w] = (uint32_t)*r++;
-    d.dead_dirty[e] = 0xffffffffu;
-}
-
-// ---------------------------------------------------------------------------
-// observation-state records (zs_obs_state.hpp): k_obs_state_pack copies the nine per-env arrays the
-// observation encoders read into one record per env, k_obs_state_unpack copies records into a viewer's envs.
-// Both walk a record in 16-B chunks, `wpe` waves of a 256-thread workgroup per env (1: four envs per
-// workgroup, 4: one), grid-stride over envs.  The record side is 16-B aligned (one 16-B store / load per
-// chunk).  The engine side is not: a [N][E] int32 row starts at byte 4 e E and a section at any 4-B offset
-// of the record, so a chunk inside one 4-byte section moves as 16 B when its engine address allows and as
-// four dwords otherwise; eight int16 HP elements of a record chunk are 32 B of the env's int32 row (two 16-B
-// accesses when aligned, else eight dwords); the u8 rows and a chunk that straddles sections move by element.
-// ---------------------------------------------------------------------------
-// the engine-side word of the record's dword at byte b (b % 4 == 0, b inside the 4-byte sections); *sec: its section
-__device__ __forceinline__ uint32_t* os_word(const Dev& d, const ObsStateLayout& L, size_t e, int b, int* sec) {
-    if (b >= L.obst_hp) return *sec = 6, (uint32_t*)d.obst_hp + e * d.O + ((b - L.obst_hp) >> 2);
-    if (b >= L.obst_present) return *sec = 5, d.obst_present + e * d.OW + ((b - L.obst_present) >> 2);
-    if (b >= L.dead) return *sec = 4, d.dead + e * d.DW + ((b - L.dead) >> 2);
-    if (b >= L.life) return *sec = 3, (uint32_t*)d.life + e * d.E + ((b - L.life) >> 2);
-    if (b >= L.pos) return *sec = 2, (uint32_t*)d.pos + e * d.E + ((b - L.pos) >> 2);
-    if (b >= L.dead_dirty) return *sec = 1, d.dead_dirty + e;
-    return *sec = 0, d.hp_dirty + e;
-}
-
-// the record's two bytes at p (p % 2 == 0) past the 4-byte sections: an int16 HP element, u8 rows, padding
-__device__ __forceinline__ uint32_t os_tail_get(const Dev& d, const ObsStateLayout& L, size_t e, int p) {
-    if (p < L.weapon) return (uint16_t)(int16_t)max(-32768, min(d.obst_hp[e * d.O + ((p - L.obst_hp) >> 1)], 32767));
-    uint32_t v = 0;
-    for (int k = 0; k < 2; k++) {
-        const int q = p + k;
-        const uint32_t by = q < L.present ? d.weapon[e * d.E + (q - L.weapon)] : q < L.pad ? d.present[e * d.E + (q - L.present)] : 0u;
-        v |= by << (8 * k);
-    }
-    return v;
-}
-__device__ __forceinline__ void os_tail_put(const Dev& d, const ObsStateLayout& L, size_t e, int p, uint32_t v) {
-    if (p < L.weapon) {
-        d.obst_hp[e * d.O + ((p - L.obst_hp) >> 1)] = (int32_t)(int16_t)(v & 0xffffu);
-        return;
-    }
-    for (int k = 0; k < 2; k++) {
-        const int q = p + k;
-        const uint8_t by = (uint8_t)(v >> (8 * k));
-        if (q < L.present) d.weapon[e * d.E + (q - L.weapon)] = by;
-        else if (q < L.pad) d.present[e * d.E + (q - L.present)] = by;
-    }
-}
-
-// rec [n][L.rec_bytes]: record r is env env0 + r of the handle; PACK: engine -> record, else record -> engine
-template <bool PACK>
-__device__ __forceinline__ void obs_state_copy(const Dev& d, const ObsStateLayout& L, int wpe, int env0, int n, uint4* rec) {
-    const int team = wpe * 64, per_wg = 256 / team;
-    const int t = threadIdx.x % team;
-    const int nch = L.rec_bytes >> 4;
-    const int words_end = L.hp_bytes == 4 ? L.weapon : L.obst_hp;  // end of the 4-byte sections
-    for (int r = blockIdx.x * per_wg + threadIdx.x / team; r < n; r += gridDim.x * per_wg) {
-        const size_t e = (size_t)(env0 + r);
-        uint4* row = rec + (size_t)r * nch;
-        for (int c = t; c < nch; c += team) {
-            const int b0 = c << 4;
-            uint32_t w[4];
-            if (!PACK) {
-                const uint4 v = row[c];
-                w[0] = v.x, w[1] = v.y, w[2] = v.z, w[3] = v.w;
-            }
-            if (b0 + 16 <= words_end) {
-                int s0, s3;
-                uint32_t* p0 = os_word(d, L, e, b0, &s0);
-                (void)os_word(d, L, e, b0 + 12, &s3);
-                if (s0 == s3 && ((uintptr_t)p0 & 15) == 0) {  // one section, 16-B aligned on the engine side
-                    if (PACK) row[c] = *(const uint4*)p0;
-                    else *(uint4*)p0 = uint4{w[0], w[1], w[2], w[3]};
-                    continue;
-                }
-            }
-            if (L.hp_bytes == 2 && b0 >= L.obst_hp && b0 + 16 <= L.weapon) {
-                // eight int16 HP elements of the record = 32 B of the env's int32 row, all loads issued first
-                int32_t* p = d.obst_hp + e * d.O + ((b0 - L.obst_hp) >> 1);
-                const bool al = ((uintptr_t)p & 15) == 0;
-                int v[8];
-                if (PACK) {
-                    if (al) {
-                        const int4 lo = ((const int4*)p)[0], hi = ((const int4*)p)[1];
-                        v[0] = lo.x, v[1] = lo.y, v[2] = lo.z, v[3] = lo.w, v[4] = hi.x, v[5] = hi.y, v[6] = hi.z, v[7] = hi.w;
-                    } else {
-#pragma unroll
-                        for (int k = 0; k < 8; k++) v[k] = p[k];
-                    }
-#pragma unroll
-                    for (int j = 0; j < 4; j++)
-                        w[j] = (uint32_t)(uint16_t)(int16_t)max(-32768, min(v[2 * j], 32767)) |
-                               ((uint32_t)(uint16_t)(int16_t)max(-32768, min(v[2 * j + 1], 32767)) << 16);
-                    row[c] = uint4{w[0], w[1], w[2], w[3]};
-                } else {
-#pragma unroll
-                    for (int j = 0; j < 4; j++) v[2 * j] = (int16_t)(w[j] & 0xffffu), v[2 * j + 1] = (int16_t)(w[j] >> 16);
-                    if (al) {
-                        ((int4*)p)[0] = int4{v[0], v[1], v[2], v[3]};
-                        ((int4*)p)[1] = int4{v[4], v[5], v[6], v[7]};
-                    } else {
-#pragma unroll
-                        for (int k = 0; k < 8; k++) p[k] = v[k];
-                    }
-                }
-                continue;
-            }
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                const int b = b0 + 4 * j;
-                if (b < words_end) {
-                    int s;
-                    uint32_t* p = os_word(d, L, e, b, &s);
-                    if (PACK) w[j] = *p;
-                    else *p = w[j];
-                } else if (PACK) {
-                    w[j] = os_tail_get(d, L, e, b) | (os_tail_get(d, L, e, b + 2) << 16);
-                } else {
-                    os_tail_put(d, L, e, b, w[j]);
-                    os_tail_put(d, L, e, b + 2, w[j] >> 16);
-                }
-            }
-            if (PACK) row[c] = uint4{w[0], w[1], w[2], w[3]};
-        }
-    }
-}
-
-__global__ __launch_bounds__(256) void k_obs_state_pack(Dev d, ObsStateLayout L, int wpe, int n, uint4* rec) {
-    obs_state_copy<true>(d, L, wpe, 0, n, rec);
-}
-__global__ __launch_bounds__(256) void k_obs_state_unpack(Dev d, ObsStateLayout L, int wpe, int env0, int n, const uint4* rec) {
-    obs_state_copy<false>(d, L, wpe, env0, n, (uint4*)rec);
-}
-
-// ---------------------------------------------------------------------------
-// snapshot records (zs_snapshot.hpp): k_snapshot copies everything per-env into one record per entry,
-// k_restore copies records back into envs, k_pending_list rebuilds the pending-reset list from the flags.
-// One 256-thread workgroup per entry (the MT ring alone is 312 chunks), grid-stride over entries; each kernel is a
-// loop over (record, 16-B chunk) that calls the record walker (zs_record.hpp: the section table and
-// rec_copy_chunk).  The table comes by value (the section search reads it there, in scalar registers) and is
-// staged in LDS so a lane can index it by section.
-// ---------------------------------------------------------------------------
-static_assert(ZS_SNAP_NSCAL == S_NSCAL && ZS_SNAP_RING == ZS_RING_WORDS, "zs_snapshot.hpp mirrors zs_device.hpp");
-static_assert(SNAP_NSEC + 1 <= REC_MAX_SEC, "a snapshot record's sections (with env_params) fit a table");
-static_assert(ZS_SNAP_ENVP == 2 * EP_N, "the env_params section is both triples");
-
-__device__ __forceinline__ void rec_stage_table(const RecTable& arg, RecTable* lds) {
-    static_assert(sizeof(RecTable) % 4 == 0, "dword copy");
-    const uint32_t* src = (const uint32_t*)&arg;
-    for (int k = threadIdx.x; k < (int)(sizeof(RecTable) / 4); k += blockDim.x) ((uint32_t*)lds)[k] = src[k];
-    __syncthreads();
-}
-
-// record k = env idx[k] (idx NULL: env k); an index outside [0, N) is skipped
-__global__ __launch_bounds__(256) void k_snapshot(RecTable tab, int N, const int32_t* idx, int n, uint4* rec) {
-    __shared__ RecTable T;
-    rec_stage_table(tab, &T);
-    const int nch = tab.rec_bytes >> 4;
-    for (int k = blockIdx.x; k < n; k += gridDim.x) {
-        const int e = idx ? idx[k] : k;
-        if ((unsigned)e >= (unsigned)N) continue;
-        RecChunk* row = (RecChunk*)(rec + (size_t)k * nch);
-        for (int c = threadIdx.x; c < nch; c += 256) rec_copy_chunk<true>(tab, T, row, (size_t)e, c);
-    }
-}
-
-// record src[k] (NULL: k) of the n_records at rec into env dst[k] (NULL: k); an entry whose record or env is out
-// of range is skipped.  The written envs' log counts are zeroed (the logs are a step's outputs), and *list_count
-// for k_pending_list, which follows on the stream.
-__global__ __launch_bounds__(256) void k_restore(RecTable tab, int N, int32_t* dlog_n, int32_t* alog_n, const int32_t* src,
-                                                 const int32_t* dst, int n, int n_records, const uint4* rec, int* list_count) {
-    __shared__ RecTable T;
-    rec_stage_table(tab, &T);
-    if (blockIdx.x == 0 && threadIdx.x == 0) *list_count = 0;
-    const int nch = tab.rec_bytes >> 4;
-    for (int k = blockIdx.x; k < n; k += gridDim.x) {
-        const int r = src ? src[k] : k, e = dst ? dst[k] : k;
-        if ((unsigned)r >= (unsigned)n_records || (unsigned)e >= (unsigned)N) continue;
-        RecChunk* row = (RecChunk*)rec + (size_t)r * nch;
-        for (int c = threadIdx.x; c < nch; c += 256) rec_copy_chunk<false>(tab, T, row, (size_t)e, c);
-        if (threadIdx.x == 0 && dlog_n) dlog_n[e] = 0, alog_n[e] = 0;
-    }
-}
-
-// list = the envs whose S_NEEDRESET is set, in any order (envs are independent); *count starts at zero
-// (k_restore).  One atomic per wave: its flagged lanes take consecutive entries.
-__global__ __launch_bounds__(256) void k_pending_list(const int32_t* needs_reset, int N, int* list, int* count) {
-    const int lane = threadIdx.x & 63;
-    for (int e0 = (blockIdx.x * 256 + threadIdx.x) - lane; e0 < N; e0 += gridDim.x * 256) {
-        const int e = e0 + lane;
-        const bool f = e < N && needs_reset[e] != 0;
-        const unsigned long long m = __ballot(f);
-        if (!m) continue;
-        int base = 0;
-        if (lane == 0) base = atomicAdd(count, __popcll(m));
-        base = __shfl(base, 0);
-        const int k = base + __popcll(m & ((1ull << lane) - 1ull));
-        if (f && (unsigned)k < (unsigned)N) list[k] = e;
-    }
-}
-
-__global__ void k_init_pending(Dev d, int* list, int* count) {
-    int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e == 0) {
-        count[0] = d.N;
-        count[1] = 0;
-    }
-    if (e >= d.N) return;
-    list[e] = e;
-    d.scal[S_NEEDRESET * d.N + e] = 1;
-}
-
-__global__ void k_init_obstacles(Dev d) {
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (size_t)d.N * d.O) return;
-    int o = (int)(i % d.O);
-    d.obst_hp[i] = d.obst_kind[o] == ZS_THING_BOX ? 10 : 200;  // Box / Wall MAX_LIFE
-}
+#include "zs_mask.hpp"  // the mask launch's geometry (zs_describe); the kernel is k_mask.hip's
 
 // ===========================================================================
 // host side: C ABI
@@ -558,7 +103,7 @@ struct zs_handle {
     // diagnostics: HIP events bracketing every k_tick / k_obs launch on its stream
     int prof = 0;
     std::vector<hipEvent_t> ev_pool;
-    std::vector<std::pair<int, int>> ev_tick, ev_obs, ev_reset, ev_respawn;  // (start, end) indices into ev_pool
+    std::vector<std::pair<int, int>> ev_tick, ev_obs, ev_reset, ev_respawn;  // (start, end) indices into ev_pool (EventList)
     size_t ev_next = 0;
 };
 
@@ -570,6 +115,55 @@ static hipEvent_t prof_event(zs_handle* h, int* idx) {
     }
     *idx = (int)h->ev_next;
     return h->ev_pool[h->ev_next++];
+}
+
+typedef std::vector<std::pair<int, int>> EventList;
+
+// launch() (a hipError_t; `what` names it in the error text) on s, between two events of a profiling handle
+// (zs_profile), the pair appended to `list`
+template <typename F>
+static int timed_launch(zs_handle* h, hipStream_t s, EventList& list, const char* what, F launch) {
+    int i0 = -1, i1 = -1;
+    if (h->prof) HIPCHK(hipEventRecord(prof_event(h, &i0), s));
+    const hipError_t e = launch();
+    if (e != hipSuccess) return fail(ZS_EHIP, std::string(what) + ": " + hipGetErrorString(e));
+    if (h->prof) {
+        HIPCHK(hipEventRecord(prof_event(h, &i1), s));
+        list.push_back({i0, i1});
+    }
+    return ZS_OK;
+}
+
+// zs_profile, zs_profile_read: nothing recorded, every pooled event free again
+static void prof_clear(zs_handle* h) {
+    for (EventList* l : {&h->ev_tick, &h->ev_obs, &h->ev_reset, &h->ev_respawn}) l->clear();
+    h->ev_next = 0;
+}
+
+// both graphs of a set destroyed (the first failure's status returned, the rest still destroyed)
+static hipError_t destroy_graphs(zs_handle::GraphSet& gs) {
+    hipError_t first = hipSuccess;
+    for (hipGraphExec_t& g : gs.g) {
+        const hipError_t e = g ? hipGraphExecDestroy(g) : hipSuccess;
+        if (first == hipSuccess) first = e;
+        g = nullptr;
+    }
+    return first;
+}
+
+// the error word of the launches queued on s, read back and left clear (every reader leaves it clear); synchronises s
+static int read_error_word(zs_handle* h, hipStream_t s, int* err) {
+    *err = 0;
+    HIPCHK(hipMemcpyAsync(err, h->d_err, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemsetAsync(h->d_err, 0, sizeof(int), s));
+    HIPCHK(hipStreamSynchronize(s));
+    return ZS_OK;
+}
+
+// what a reset's error word means to the caller (zs_reset, the drop-ins' per-call path)
+static int reset_result(int err) {
+    if (err == ZS_ENOSPACE) return fail(ZS_ENOSPACE, "Not enough space to spawn players/agents");
+    return err ? fail(err, "reset failed") : ZS_OK;
 }
 
 extern "C" const char* zs_last_error(void) { return g_err.c_str(); }
@@ -604,6 +198,15 @@ static int dupload(zs_handle* h, T** p, const std::vector<T>& v) {
     return ZS_OK;
 }
 
+// the same into one of Dev's read-only tables
+template <typename T>
+static int dupload(zs_handle* h, const T** p, const std::vector<T>& v) {
+    T* q = nullptr;
+    const int rc = dupload(h, &q, v);
+    *p = q;
+    return rc;
+}
+
 static void free_all(zs_handle* h) {
     for (void* p : h->allocs) (void)hipFree(p);
     h->allocs.clear();
@@ -615,12 +218,7 @@ static void free_all(zs_handle* h) {
     h->ev_rfork = h->ev_rjoin = nullptr;
     if (h->s_reset) (void)hipStreamDestroy(h->s_reset);
     h->s_reset = nullptr;
-    for (auto& gs : h->gsets)
-        for (hipGraphExec_t& g : gs.g)
-            if (g) {
-                (void)hipGraphExecDestroy(g);
-                g = nullptr;
-            }
+    for (auto& gs : h->gsets) (void)destroy_graphs(gs);
     for (hipEvent_t ev : h->ev_pool) (void)hipEventDestroy(ev);
     h->ev_pool.clear();
 }
@@ -754,25 +352,19 @@ static int create_static_tables(zs_handle* h, const zs_config* cfg, bool* rank_o
     std::vector<int32_t> ac(cfg->agent_codes, cfg->agent_codes + d.A);
     std::vector<int32_t> bt(cfg->bot_types, cfg->bot_types + d.P);
 
-
-    int16_t* p_cellmap;
-    uint32_t *p_objbits, *p_obstbits, *p_boxbits;
-    int32_t *p_scell, *p_oprefix;
-    int32_t *p_oxy, *p_ps, *p_zs, *p_aw, *p_ac, *p_bt;
-    uint8_t* p_okind;
-    TRY(dupload(h, &p_cellmap, cellmap));
-    TRY(dupload(h, &p_objbits, objbits));
-    TRY(dupload(h, &p_obstbits, obstbits));
-    TRY(dupload(h, &p_scell, scell));
-    TRY(dupload(h, &p_boxbits, boxbits));
-    TRY(dupload(h, &p_oprefix, oprefix));
-    TRY(dupload(h, &p_oxy, oxy));
-    TRY(dupload(h, &p_okind, okind));
-    TRY(dupload(h, &p_ps, ps));
-    TRY(dupload(h, &p_zs, zs));
-    TRY(dupload(h, &p_aw, aw));
-    TRY(dupload(h, &p_ac, ac));
-    TRY(dupload(h, &p_bt, bt));
+    TRY(dupload(h, &d.cellmap, cellmap));
+    TRY(dupload(h, &d.objbits, objbits));
+    TRY(dupload(h, &d.obstbits, obstbits));
+    TRY(dupload(h, &d.scell, scell));
+    TRY(dupload(h, &d.boxbits, boxbits));
+    TRY(dupload(h, &d.oprefix, oprefix));
+    TRY(dupload(h, &d.obst_xy, oxy));
+    TRY(dupload(h, &d.obst_kind, okind));
+    TRY(dupload(h, &d.pspawn, ps));
+    TRY(dupload(h, &d.zspawn, zs));
+    TRY(dupload(h, &d.agent_weapons, aw));
+    TRY(dupload(h, &d.agent_codes, ac));
+    TRY(dupload(h, &d.bot_types, bt));
     {
         // k_obs_patch's tables (zs_obs.hpp): the map padded by half a registered window (21) on every
         // side, each cell the code / life it shows with no thing on it, no body, every obstacle present
@@ -801,28 +393,11 @@ static int create_static_tables(zs_handle* h, const zs_config* cfg, bool* rank_o
             opk[i] = (uint32_t)(x & 0xfff) | ((uint32_t)(y & 0xfff) << 12) | ((okind[i] == ZS_THING_BOX ? 1u : 0u) << 24) |
                      (((objbits[c >> 5] >> (c & 31)) & 1u) << 25);
         }
-        uint16_t* p_pad;
-        uint32_t* p_opk;
-        TRY(dupload(h, &p_pad, pad));
-        TRY(dupload(h, &p_opk, opk));
-        d.opad = p_pad;
+        TRY(dupload(h, &d.opad, pad));
+        TRY(dupload(h, &d.opk, opk));
         d.opad_w = pw;
         d.opad_n = pw * ph;
-        d.opk = p_opk;
     }
-    d.cellmap = p_cellmap;
-    d.objbits = p_objbits;
-    d.obstbits = p_obstbits;
-    d.scell = p_scell;
-    d.boxbits = p_boxbits;
-    d.oprefix = p_oprefix;
-    d.obst_xy = p_oxy;
-    d.obst_kind = p_okind;
-    d.pspawn = p_ps;
-    d.zspawn = p_zs;
-    d.agent_weapons = p_aw;
-    d.agent_codes = p_ac;
-    d.bot_types = p_bt;
     return ZS_OK;
 }
 
@@ -846,17 +421,13 @@ static int create_env_arrays(zs_handle* h, const zs_map_desc& m) {
     {
         std::vector<int32_t> init(std::max(d.O, 1), 0);
         for (int i = 0; i < d.O; i++) init[i] = m.obstacle_kind[i] == ZS_THING_BOX ? 10 : 200;  // Box / Wall MAX_LIFE
-        int32_t* p_init;
-        TRY(dupload(h, &p_init, init));
-        d.hp_init = p_init;
+        TRY(dupload(h, &d.hp_init, init));
         d.hp_chunk = std::max(1, (d.O + 31) / 32);
         d.hp_chunk_m = (uint32_t)(((1u << 20) + d.hp_chunk - 1) / d.hp_chunk);
         d.hp_chunk_m32 = (uint32_t)(((1ull << 32) + d.hp_chunk - 1) / d.hp_chunk);
         std::vector<uint32_t> full(std::max(d.OW, 1), 0u);
         for (int w = 0; w < d.OW; w++) full[w] = d.O - 32 * w >= 32 ? 0xffffffffu : ((1u << (d.O - 32 * w)) - 1u);
-        uint32_t* p_full;
-        TRY(dupload(h, &p_full, full));
-        d.opres_full = p_full;
+        TRY(dupload(h, &d.opres_full, full));
     }
     TRY(dalloc(h, &d.obst_present, (size_t)d.OW * N));
     TRY(dalloc(h, &d.obst_nonpos, (size_t)d.OW * N));
@@ -864,9 +435,7 @@ static int create_env_arrays(zs_handle* h, const zs_map_desc& m) {
     TRY(dalloc(h, &d.dead_dirty, N));
     {
         std::vector<uint32_t> zero(std::max(d.DW, 1), 0u);
-        uint32_t* p_zero;
-        TRY(dupload(h, &p_zero, zero));
-        d.dead_zero = p_zero;
+        TRY(dupload(h, &d.dead_zero, zero));
         d.dead_chunk = std::max(1, (d.DW + 31) / 32);
         d.dead_chunk_m = (uint32_t)(((1u << 20) + d.dead_chunk - 1) / d.dead_chunk);
         d.dead_chunk_m32 = (uint32_t)(((1ull << 32) + d.dead_chunk - 1) / d.dead_chunk);
@@ -1004,19 +573,11 @@ extern "C" int zs_create(const zs_config* cfg, int device, zs_handle** out) {
                 d.fobs, d.obsl.bytes, obs_kernel_name(kf.kind), obs_grid(kf, d.N), kf.block, kf.lds,
                 obs_kernel_name(km.kind), km.block, km.lds, h->reset_side, d.defer_respawn);
     }
-    if (d.O > 0) {
-        size_t n = N * d.O;
-        hipLaunchKernelGGL(k_init_obstacles, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, d);
-        hipError_t le = hipGetLastError();
-        if (le != hipSuccess) return fail(ZS_EHIP, std::string("k_init_obstacles: ") + hipGetErrorString(le));
-    }
+    if (d.O > 0) HIPCHK(launch_init_obstacles(0, d));
     // every env starts "pending reset": the first zs_step (or zs_reset) builds its world
-    hipLaunchKernelGGL(k_init_pending, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, 0, d, h->d_rlist[0],
-                       h->d_rcount);
-    if (d.flags & ZS_FLAG_ENV_PARAMS) {  // both triples of every env start as the config's values
-        const hipError_t pe = launch_env_params_init(0, d, h->d_envp_owner);
-        if (pe != hipSuccess) return fail(ZS_EHIP, std::string("k_env_params_init: ") + hipGetErrorString(pe));
-    }
+    HIPCHK(launch_init_pending(0, d, h->d_rlist[0], h->d_rcount));
+    // both triples of every env start as the config's values
+    if (d.flags & ZS_FLAG_ENV_PARAMS) HIPCHK(launch_env_params_init(0, d, h->d_envp_owner));
     // default seeds: env index (every env has a valid stream even if never seeded)
     std::vector<uint64_t> seeds(N);
     for (size_t i = 0; i < N; i++) seeds[i] = i;
@@ -1052,8 +613,7 @@ static int seed_envs(zs_handle* h, int32_t env0, int32_t n, const uint64_t* seed
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipMemcpyAsync(h->d_seedbuf, seeds_host, sizeof(uint64_t) * n, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_seed, dim3((n + 63) / 64), dim3(64), 0, s, h->d, env0, n, h->d_seedbuf);
-    HIPCHK(hipGetLastError());
+    HIPCHK(launch_seed(s, h->d, env0, n, h->d_seedbuf));
     HIPCHK(hipStreamSynchronize(s));  // seeds_host may be freed by the caller on return
     return ZS_OK;
 }
@@ -1070,93 +630,48 @@ static const TickUnit& tick_unit(int G) {
     return units[__builtin_ctz((unsigned)G)];
 }
 
-static int launch_obs(zs_handle* h, void* obs, const uint8_t* mask, hipStream_t s, int env0 = 0, int env1 = -1) {
-    const Dev& d = h->d;
+// The step's launches take the Dev they pass to the kernels: the handle's, or zs_step's copy of it with the policy
+// and the tail set (Dev::pol_*, Dev::tail_*).
+static int launch_obs(zs_handle* h, const Dev& d, void* obs, const uint8_t* mask, hipStream_t s, int env0 = 0, int env1 = -1) {
     if (!obs) return ZS_OK;
-    int i0 = -1, i1 = -1;
-    if (h->prof) HIPCHK(hipEventRecord(prof_event(h, &i0), s));
     if (env1 < 0) env1 = d.N;
-    ObsLaunch o;
-    o.k = mask ? h->obs.masked : h->obs.full;
-    o.grid = obs_grid(o.k, env1 - env0);
-    o.obs = obs;
-    o.mask = mask;
-    o.env0 = env0;
-    o.env1 = env1;
-    HIPCHK(obs_launch(d.obs_dtype, o, s, d));
-    if (h->prof) {
-        HIPCHK(hipEventRecord(prof_event(h, &i1), s));
-        h->ev_obs.push_back({i0, i1});
-    }
-    return ZS_OK;
+    const ObsKernel& k = mask ? h->obs.masked : h->obs.full;
+    const ObsLaunch o = {k, obs_grid(k, env1 - env0), obs, mask, env0, env1};
+    return timed_launch(h, s, h->ev_obs, "observation launch", [&] { return obs_launch(d.obs_dtype, o, s, d); });
 }
 
-static int launch_tick(zs_handle* h, const int32_t* actions, double* rew, uint8_t* done, uint8_t* trunc,
+static int launch_tick(zs_handle* h, const Dev& d, const int32_t* actions, double* rew, uint8_t* done, uint8_t* trunc,
                        uint8_t* listed, uint8_t* reset_out, int* rlist, int* rcount, void* obs, hipStream_t s,
                        int env0 = 0, int env1 = -1) {
-    const Dev& d = h->d;
     const StepPlan& sp = h->step;
     const int ne = 64 / sp.G;
     if (env1 < 0) env1 = d.N;
     unsigned grid = (unsigned)((env1 - env0 + ne - 1) / ne);
-    int i0 = -1, i1 = -1;
     const int p = h->rpar;
-    if (h->prof) HIPCHK(hipEventRecord(prof_event(h, &i0), s));
-    TickArgs a;
-    a.actions = actions;
-    a.rew = rew;
-    a.done = done;
-    a.trunc = trunc;
-    a.listed = listed;
-    a.reset_out = reset_out;
-    a.rlist = rlist;
-    a.rcount = rcount;
-    a.obs = obs;
-    a.env0 = env0;
-    a.env1 = env1;
-    a.n_reset = sp.n_reset;
-    a.cur_list = (const int*)h->d_rlist[p];
-    a.cur_count = (const int*)(h->d_rcount + p);
-    a.err = h->d_err;
-    HIPCHK(tick_unit(sp.G).launch(sp.fused, sp.tick_waves, grid, (size_t)sp.lds, s, d, a));
-    if (h->prof) {
-        HIPCHK(hipEventRecord(prof_event(h, &i1), s));
-        h->ev_tick.push_back({i0, i1});
-    }
-    return ZS_OK;
+    const TickArgs a = {actions, rew,  done, trunc,      listed,        reset_out,       rlist,   rcount,
+                        obs,     env0, env1, sp.n_reset, h->d_rlist[p], h->d_rcount + p, h->d_err};
+    return timed_launch(h, s, h->ev_tick, "step launch",
+                        [&] { return tick_unit(sp.G).launch(sp.fused, sp.tick_waves, grid, (size_t)sp.lds, s, d, a); });
 }
 
-static int launch_reset(zs_handle* h, int list_mode, const uint8_t* mask, void* obs, hipStream_t s) {
-    const Dev& d = h->d;
+static int launch_reset(zs_handle* h, const Dev& d, int list_mode, const uint8_t* mask, void* obs, hipStream_t s) {
     const unsigned grid = (unsigned)(list_mode ? h->step.reset_grid_list : h->step.reset_grid_mask);
-    int p = h->rpar;
-    int i0 = -1, i1 = -1;
-    if (h->prof) HIPCHK(hipEventRecord(prof_event(h, &i0), s));
-    HIPCHK(launch_reset_k(grid, (size_t)h->step.reset_lds, s, d, list_mode, h->d_rlist[p], h->d_rcount + p, mask, h->d_err, obs));
-    if (h->prof) {
-        HIPCHK(hipEventRecord(prof_event(h, &i1), s));
-        h->ev_reset.push_back({i0, i1});
-    }
-    return ZS_OK;
+    const int p = h->rpar;
+    return timed_launch(h, s, h->ev_reset, "k_reset", [&] {
+        return launch_reset_k(grid, (size_t)h->step.reset_lds, s, d, list_mode, h->d_rlist[p], h->d_rcount + p, mask, h->d_err, obs);
+    });
 }
 
 // the respawns the tick just deferred (k_respawn drains d.resp_list; count zeroed before the tick)
-static int launch_respawn(zs_handle* h, hipStream_t s) {
-    const Dev& d = h->d;
-    int i0 = -1, i1 = -1;
-    if (h->prof) HIPCHK(hipEventRecord(prof_event(h, &i0), s));
-    HIPCHK(launch_respawn_k((unsigned)h->step.respawn_grid, (size_t)h->step.reset_lds, s, d));
-    if (h->prof) {
-        HIPCHK(hipEventRecord(prof_event(h, &i1), s));
-        h->ev_respawn.push_back({i0, i1});
-    }
-    return ZS_OK;
+static int launch_respawn(zs_handle* h, const Dev& d, hipStream_t s) {
+    return timed_launch(h, s, h->ev_respawn, "k_respawn",
+                        [&] { return launch_respawn_k((unsigned)h->step.respawn_grid, (size_t)h->step.reset_lds, s, d); });
 }
 
 // zs_reset's launches, queued on s (the caller synchronises and reads h->d_err)
 static int queue_reset(zs_handle* h, const uint8_t* env_mask_dev, void* obs_dev, hipStream_t s) {
     HIPCHK(hipMemsetAsync(h->d_err, 0, sizeof(int), s));
-    int rc = launch_reset(h, 0, env_mask_dev, nullptr, s);
+    int rc = launch_reset(h, h->d, 0, env_mask_dev, nullptr, s);
     if (rc) return rc;
     // the pending-reset list must hold exactly the envs still pending: drop the ones just rebuilt
     {
@@ -1173,7 +688,7 @@ static int queue_reset(zs_handle* h, const uint8_t* env_mask_dev, void* obs_dev,
             h->rpar = q;
         }
     }
-    return launch_obs(h, obs_dev, env_mask_dev, s);
+    return launch_obs(h, h->d, obs_dev, env_mask_dev, s);
 }
 
 extern "C" int zs_reset(zs_handle* h, const uint8_t* env_mask_dev, void* obs_dev, void* stream) {
@@ -1183,13 +698,9 @@ extern "C" int zs_reset(zs_handle* h, const uint8_t* env_mask_dev, void* obs_dev
     HIPCHK(hipSetDevice(h->device));
     int rc = queue_reset(h, env_mask_dev, obs_dev, s);
     if (rc) return rc;
-    int err = 0;
-    HIPCHK(hipMemcpyAsync(&err, h->d_err, sizeof(int), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemsetAsync(h->d_err, 0, sizeof(int), s));  // every reader leaves the error word clear
-    HIPCHK(hipStreamSynchronize(s));
-    if (err == ZS_ENOSPACE) return fail(ZS_ENOSPACE, "Not enough space to spawn players/agents");
-    if (err) return fail(err, "reset failed");
-    return ZS_OK;
+    int err;
+    if ((rc = read_error_word(h, s, &err))) return rc;
+    return reset_result(err);
 }
 
 // Observation only (the reference's env.get_observation(), gym_env.py:93-94): re-encode the
@@ -1198,7 +709,7 @@ extern "C" int zs_observe(zs_handle* h, const uint8_t* env_mask_dev, void* obs_d
     if (!h || !obs_dev) return fail(ZS_EINVAL, "null argument");
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(hipSetDevice(h->device));
-    return launch_obs(h, obs_dev, env_mask_dev, s);
+    return launch_obs(h, h->d, obs_dev, env_mask_dev, s);
 }
 
 extern "C" int zs_step(zs_handle* h, const int32_t* actions_dev, void* obs_dev, double* rewards_dev, uint8_t* done_dev,
@@ -1224,24 +735,17 @@ extern "C" int zs_step(zs_handle* h, const int32_t* actions_dev, void* obs_dev, 
         // starts the policy first: C3 173 M env-steps/s, against 167 with the reset launch captured first
         // and 169 with the policy inside the step launch); otherwise inside the step launch (no launch,
         // no gap: 8 192 envs 110 -> 117 M env-steps/s)
-        if (h->graph_pol && side) {
-            const int n = h->d.N * h->d.A;
-            hipLaunchKernelGGL(k_gen_actions_ctr, dim3((n + 255) / 256), dim3(256), 0, s, h->d,
-                               (const uint64_t*)h->d_gstep, h->graph_pol, (int32_t*)actions_dev);
-            HIPCHK(hipGetLastError());
-        }
-        rc = launch_reset(h, 1, nullptr, h->d.fobs ? obs_dev : nullptr, rs);
+        if (h->graph_pol && side)
+            HIPCHK(launch_gen_actions_ctr(s, h->d, (const uint64_t*)h->d_gstep, h->graph_pol, (int32_t*)actions_dev));
+        rc = launch_reset(h, h->d, 1, nullptr, h->d.fobs ? obs_dev : nullptr, rs);
         if (rc) return rc;
         if (side) HIPCHK(hipEventRecord(h->ev_rjoin, h->s_reset));
     }
-    struct PolScope {
-        Dev& d;
-        PolScope(Dev& dd, int n, const uint64_t* st) : d(dd) {
-            d.pol_n = n;
-            d.pol_step = st;
-        }
-        ~PolScope() { d.pol_n = 0, d.pol_step = nullptr; }
-    } pol(h->d, side ? 0 : h->graph_pol, side ? nullptr : h->d_gstep);
+    // this step's Dev: the handle's (whose pol_* and tail_* stay null) with the policy the step launch generates
+    // itself, then (below) with the tail the step's last launch carries
+    Dev d = h->d;
+    d.pol_n = side ? 0 : h->graph_pol;
+    d.pol_step = side ? nullptr : h->d_gstep;
     // 2) tick every other env; envs that end now are queued on list[q] for the next call.
     // Work-list counters: between calls the list the next step appends to (list[1 - rpar]) and the
     // deferred-respawn list are empty.  This step appends to list[q] and resp_list, drains list[p] and
@@ -1252,7 +756,7 @@ extern "C" int zs_step(zs_handle* h, const int32_t* actions_dev, void* obs_dev, 
     // sequence standalone without a fault, profiles/r03_graphprobe_fork.log.)  Every list index is
     // bounds-checked in the kernels.
     const int p = h->rpar;
-    rc = launch_tick(h, actions_dev, rewards_dev, done_dev, trunc_dev, listed_dev, reset_dev, h->d_rlist[q],
+    rc = launch_tick(h, d, actions_dev, rewards_dev, done_dev, trunc_dev, listed_dev, reset_dev, h->d_rlist[q],
                      h->d_rcount + q, obs_dev, s);
     if (rc) return rc;
     h->rpar = q;
@@ -1268,33 +772,26 @@ extern "C" int zs_step(zs_handle* h, const int32_t* actions_dev, void* obs_dev, 
         return code;
     };
     if (h->d.defer_respawn) {
-        rc = launch_respawn(h, s);
+        rc = launch_respawn(h, d, s);
         if (rc) return tail_on_error(rc);
     }
     // join the reset work, then 3) observations of every env (already written by the step launch
     // when fobs), carrying the step's tail
     if (side && hipStreamWaitEvent(s, h->ev_rjoin, 0) != hipSuccess) return tail_on_error(fail(ZS_EHIP, "hipStreamWaitEvent"));
-    struct TailScope {
-        Dev& d;
-        TailScope(Dev& dd, int* c0, int* c1, uint64_t* st) : d(dd) {
-            d.tail_cnt0 = c0;
-            d.tail_cnt1 = c1;
-            d.tail_step = st;
-        }
-        ~TailScope() { d.tail_cnt0 = d.tail_cnt1 = nullptr, d.tail_step = nullptr; }
-    } tail(h->d, h->d_rcount + p, h->d.defer_respawn ? h->d.resp_count : nullptr, h->graph_pol ? h->d_gstep : nullptr);
-    if (h->d.fobs || !obs_dev) {
-        hipLaunchKernelGGL(k_tail, dim3(1), dim3(64), 0, s, h->d);
-        const hipError_t le = hipGetLastError();
+    d.tail_cnt0 = h->d_rcount + p;
+    d.tail_cnt1 = d.defer_respawn ? d.resp_count : nullptr;
+    d.tail_step = h->graph_pol ? h->d_gstep : nullptr;
+    if (d.fobs || !obs_dev) {
+        const hipError_t le = launch_tail(s, d);
         if (le != hipSuccess) return tail_on_error(fail(ZS_EHIP, std::string("k_tail: ") + hipGetErrorString(le)));
     } else {
-        rc = launch_obs(h, obs_dev, nullptr, s);
+        rc = launch_obs(h, d, obs_dev, nullptr, s);
         if (rc) return tail_on_error(rc);
     }
     // 4) a bound mask buffer (zs_action_mask_bind): the masks of the world the observations show, respawned
     //    zombies and reset envs included (the step's tail is done: nothing to undo when this launch fails)
     if (h->mask_bound) {
-        const hipError_t me = launch_action_mask(s, h->d, nullptr, h->mask_bound);
+        const hipError_t me = launch_action_mask(s, d, nullptr, h->mask_bound);
         if (me != hipSuccess) return fail(ZS_EHIP, std::string("k_action_mask: ") + hipGetErrorString(me));
     }
     return ZS_OK;
@@ -1327,11 +824,7 @@ extern "C" int zs_action_mask_bind(zs_handle* h, void* mask_dev_or_null) {
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipDeviceSynchronize());
     for (auto& gs : h->gsets) {
-        for (hipGraphExec_t& g : gs.g)
-            if (g) {
-                HIPCHK(hipGraphExecDestroy(g));
-                g = nullptr;
-            }
+        HIPCHK(destroy_graphs(gs));
         gs.used = 0;
     }
     h->mask_bound = mask_dev_or_null;
@@ -1344,9 +837,7 @@ extern "C" int zs_gen_actions(zs_handle* h, uint64_t step, int32_t n_discrete, i
     if (n_discrete < 1 || n_discrete > 7) return fail(ZS_EINVAL, "n_discrete must be in 1..7");
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(hipSetDevice(h->device));
-    int n = h->d.N * h->d.A;
-    hipLaunchKernelGGL(k_gen_actions, dim3((n + 255) / 256), dim3(256), 0, s, h->d, step, n_discrete, actions_dev);
-    HIPCHK(hipGetLastError());
+    HIPCHK(launch_gen_actions(s, h->d, step, n_discrete, actions_dev));
     return ZS_OK;
 }
 
@@ -1383,11 +874,7 @@ extern "C" int zs_step_graph_n(zs_handle* h, uint64_t step0, int32_t n_discrete,
         set = &h->gsets[0];
         for (auto& gs : h->gsets)
             if (gs.used < set->used) set = &gs;
-        for (hipGraphExec_t& g : set->g)
-            if (g) {
-                HIPCHK(hipGraphExecDestroy(g));
-                g = nullptr;
-            }
+        HIPCHK(destroy_graphs(*set));
         if (!h->d_gstep) {
             int rc = dalloc(h, &h->d_gstep, 2);
             if (rc) return rc;
@@ -1426,11 +913,7 @@ extern "C" int zs_step_graph_n(zs_handle* h, uint64_t step0, int32_t n_discrete,
         h->prof = prof;
         (void)hipStreamDestroy(cs);
         if (rc != ZS_OK) {
-            for (hipGraphExec_t& g : set->g)
-                if (g) {
-                    (void)hipGraphExecDestroy(g);
-                    g = nullptr;
-                }
+            (void)destroy_graphs(*set);
             return rc;
         }
         for (int k = 0; k < 9; k++) set->key[k] = key[k];
@@ -1453,8 +936,7 @@ extern "C" int zs_get_state(zs_handle* h, int32_t env, int32_t* buf_host, void* 
     if (env < 0 || env >= h->d.N) return fail(ZS_EINVAL, "env index out of range");
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(hipSetDevice(h->device));
-    hipLaunchKernelGGL(k_get_state, dim3(1), dim3(64), 0, s, h->d, env, h->d_state);
-    HIPCHK(hipGetLastError());
+    HIPCHK(launch_get_state(s, h->d, env, h->d_state));
     HIPCHK(hipMemcpyAsync(buf_host, h->d_state, sizeof(int32_t) * h->state_words, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     return ZS_OK;
@@ -1479,12 +961,10 @@ extern "C" int zs_set_state(zs_handle* h, int32_t env, const int32_t* buf_host, 
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipMemsetAsync(h->d_err, 0, sizeof(int), s));
     HIPCHK(hipMemcpyAsync(h->d_state, buf_host, sizeof(int32_t) * h->state_words, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_set_state, dim3(1), dim3(64), 0, s, h->d, env, h->d_state, h->d_err);
-    HIPCHK(hipGetLastError());
-    int err = 0;
-    HIPCHK(hipMemcpyAsync(&err, h->d_err, sizeof(int), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemsetAsync(h->d_err, 0, sizeof(int), s));
-    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(launch_set_state(s, h->d, env, h->d_state, h->d_err));
+    int err;
+    const int rc = read_error_word(h, s, &err);
+    if (rc) return rc;
     if (err) return fail(ZS_EINVAL, "state record's needs_reset [5] differs from the engine's (pending resets are not settable)");
     return ZS_OK;
 }
@@ -1502,18 +982,11 @@ extern "C" int zs_overflow(zs_handle* h, uint32_t* flags_host, int32_t clear, vo
 }
 
 // ---------------------------------------------------------------------------
-// observation-state records (zs_obs_state.hpp; kernels above)
+// observation-state records (zs_obs_state.hpp; kernels and launch geometry: k_records.hip)
 // ---------------------------------------------------------------------------
 static ObsStateLayout handle_obs_state_layout(const zs_handle* h) {
     const Dev& d = h->d;
     return obs_state_layout(d.E, d.O, d.DW, d.OW, obs_state_record_dtype(d.obs_dtype, d.obs_enc));
-}
-
-// waves of a workgroup per env (one wave walks up to four 16-B chunks per lane) and the launch's workgroups
-static void obs_state_geometry(const ObsStateLayout& L, int n, int* wpe, unsigned* grid) {
-    *wpe = L.rec_bytes > 4 * 64 * 16 ? 4 : 1;
-    const int per_wg = 4 / *wpe;
-    *grid = (unsigned)std::min((n + per_wg - 1) / per_wg, 256 * 16);  // grid-stride past 16 workgroups per CU
 }
 
 extern "C" int zs_obs_state_layout(const zs_handle* h, int32_t out[12]) {
@@ -1530,12 +1003,7 @@ extern "C" int zs_obs_state_pack(zs_handle* h, void* rec_dev, void* stream) {
     if ((uintptr_t)rec_dev & 15) return fail(ZS_EINVAL, "rec_dev must be 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(hipSetDevice(h->device));
-    const ObsStateLayout L = handle_obs_state_layout(h);
-    int wpe;
-    unsigned grid;
-    obs_state_geometry(L, h->d.N, &wpe, &grid);
-    hipLaunchKernelGGL(k_obs_state_pack, dim3(grid), dim3(256), 0, s, h->d, L, wpe, h->d.N, (uint4*)rec_dev);
-    HIPCHK(hipGetLastError());
+    HIPCHK(launch_obs_state_pack(s, h->d, handle_obs_state_layout(h), rec_dev));
     return ZS_OK;
 }
 
@@ -1550,16 +1018,12 @@ extern "C" int zs_obs_state_unpack(zs_handle* h, const void* rec_dev, int32_t re
     if (n == 0) return ZS_OK;
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(hipSetDevice(h->device));
-    int wpe;
-    unsigned grid;
-    obs_state_geometry(L, n, &wpe, &grid);
-    hipLaunchKernelGGL(k_obs_state_unpack, dim3(grid), dim3(256), 0, s, h->d, L, wpe, env0, n, (const uint4*)rec_dev);
-    HIPCHK(hipGetLastError());
+    HIPCHK(launch_obs_state_unpack(s, h->d, L, env0, n, rec_dev));
     return ZS_OK;
 }
 
 // ---------------------------------------------------------------------------
-// snapshot records (zs_snapshot.hpp; kernels above): asynchronous, no host staging
+// snapshot records (zs_snapshot.hpp; kernels and launch geometry: k_records.hip): asynchronous, no host staging
 // ---------------------------------------------------------------------------
 static SnapshotLayout handle_snapshot_layout(const zs_handle* h) {
     const Dev& d = h->d;
@@ -1590,9 +1054,6 @@ extern "C" int zs_snapshot_layout(const zs_handle* h, int32_t out[24]) {
     return ZS_OK;
 }
 
-// workgroups of a launch over n entries, one entry per workgroup at a time (grid-stride past 16 per CU)
-static unsigned snap_grid(int n) { return (unsigned)std::min(n, 256 * 16); }
-
 extern "C" int zs_snapshot(zs_handle* h, const int32_t* env_idx_dev, int32_t n, void* rec_dev, void* stream) {
     if (!h || !rec_dev) return fail(ZS_EINVAL, "null argument");
     if (n < 0) return fail(ZS_EINVAL, "n must be >= 0");
@@ -1600,9 +1061,7 @@ extern "C" int zs_snapshot(zs_handle* h, const int32_t* env_idx_dev, int32_t n, 
     if (n == 0) return ZS_OK;
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(hipSetDevice(h->device));
-    const RecTable T = snapshot_table(h);
-    hipLaunchKernelGGL(k_snapshot, dim3(snap_grid(n)), dim3(256), 0, s, T, h->d.N, env_idx_dev, n, (uint4*)rec_dev);
-    HIPCHK(hipGetLastError());
+    HIPCHK(launch_snapshot(s, snapshot_table(h), h->d.N, env_idx_dev, n, rec_dev));
     return ZS_OK;
 }
 
@@ -1618,17 +1077,12 @@ extern "C" int zs_restore(zs_handle* h, const void* rec_dev, int32_t rec_bytes, 
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(hipSetDevice(h->device));
     const Dev& d = h->d;
-    const RecTable T = snapshot_table(h);
     // the list the next step drains, rebuilt in place from the restored flags: the copy zeroes its count, the
     // list launch refills it.  rpar stays, the list the next step appends to and the respawn list are empty
     // between calls (zs_step's counter protocol), so cached step graphs stay valid.  No memset nodes (zs_step).
     const int p = h->rpar;
-    hipLaunchKernelGGL(k_restore, dim3(snap_grid(n)), dim3(256), 0, s, T, d.N, d.dlog_n, d.alog_n, src_idx_dev, dst_idx_dev,
-                       n, n_records, (const uint4*)rec_dev, h->d_rcount + p);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_pending_list, dim3((unsigned)std::min(64, (d.N + 255) / 256)), dim3(256), 0, s,
-                       (const int32_t*)(d.scal + (size_t)S_NEEDRESET * d.N), d.N, h->d_rlist[p], h->d_rcount + p);
-    HIPCHK(hipGetLastError());
+    HIPCHK(launch_restore(s, snapshot_table(h), d, src_idx_dev, dst_idx_dev, n, n_records, rec_dev, h->d_rcount + p));
+    HIPCHK(launch_pending_list(s, d.scal + (size_t)S_NEEDRESET * d.N, d.N, h->d_rlist[p], h->d_rcount + p));
     return ZS_OK;
 }
 
@@ -1704,6 +1158,18 @@ extern "C" int zs_get_rng(zs_handle* h, int32_t env, uint32_t* state_host, void*
     return ZS_OK;
 }
 
+// a getstate() block as an env's ring: slot 0 = the given block, slot 1 = its successor (x[k+624] = x[k+397] ^
+// f(x[k], x[k+1])); returns the env's rngst word (the block's index, slot 0, next block ready)
+static uint32_t ring_from_state(uint32_t* ring, const uint32_t* state) {
+    std::memcpy(ring, state, sizeof(uint32_t) * ZS_MT_N);
+    for (int k = 0; k < ZS_MT_N; k++) {
+        uint32_t a = ring[k], b = ring[k + 1], c = ring[k + ZS_MT_M];
+        uint32_t y = (a & 0x80000000u) | (b & 0x7fffffffu);
+        ring[ZS_MT_N + k] = c ^ (y >> 1) ^ ((y & 1u) ? 0x9908b0dfu : 0u);
+    }
+    return state[ZS_MT_N] | (0u << 10) | (1u << 11);
+}
+
 extern "C" int zs_set_rng(zs_handle* h, int32_t env, const uint32_t* state_host, void* stream) {
     if (!h || !state_host) return fail(ZS_EINVAL, "null argument");
     NOT_ON_VIEWER(h, "zs_set_rng");
@@ -1711,15 +1177,8 @@ extern "C" int zs_set_rng(zs_handle* h, int32_t env, const uint32_t* state_host,
     if (state_host[ZS_MT_N] > ZS_MT_N) return fail(ZS_EINVAL, "MT index out of range (0..624)");
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(hipSetDevice(h->device));
-    // slot 0 = the given block, slot 1 = its successor (x[k+624] = x[k+397] ^ f(x[k], x[k+1]))
     std::vector<uint32_t> ring(ZS_RING_WORDS);
-    std::memcpy(ring.data(), state_host, sizeof(uint32_t) * ZS_MT_N);
-    for (int k = 0; k < ZS_MT_N; k++) {
-        uint32_t a = ring[k], b = ring[k + 1], c = ring[k + ZS_MT_M];
-        uint32_t y = (a & 0x80000000u) | (b & 0x7fffffffu);
-        ring[ZS_MT_N + k] = c ^ (y >> 1) ^ ((y & 1u) ? 0x9908b0dfu : 0u);
-    }
-    uint32_t st = state_host[ZS_MT_N] | (0u << 10) | (1u << 11);
+    const uint32_t st = ring_from_state(ring.data(), state_host);
     HIPCHK(hipMemcpyAsync(h->d.ring + (size_t)env * ZS_RING_WORDS, ring.data(), sizeof(uint32_t) * ZS_RING_WORDS,
                           hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(h->d.rngst + env, &st, sizeof(uint32_t), hipMemcpyHostToDevice, s));
@@ -1733,11 +1192,7 @@ extern "C" int zs_set_rng(zs_handle* h, int32_t env, const uint32_t* state_host,
 extern "C" int zs_profile(zs_handle* h, int32_t enable) {
     if (!h) return fail(ZS_EINVAL, "null handle");
     h->prof = enable ? 1 : 0;
-    h->ev_tick.clear();
-    h->ev_obs.clear();
-    h->ev_reset.clear();
-    h->ev_respawn.clear();
-    h->ev_next = 0;
+    prof_clear(h);
     return ZS_OK;
 }
 
@@ -1745,7 +1200,7 @@ extern "C" int zs_profile_read(zs_handle* h, double* out) {
     if (!h || !out) return fail(ZS_EINVAL, "null argument");
     HIPCHK(hipSetDevice(h->device));
     double tot[4] = {0.0, 0.0, 0.0, 0.0};
-    std::vector<std::pair<int, int>>* lists[4] = {&h->ev_tick, &h->ev_obs, &h->ev_reset, &h->ev_respawn};
+    EventList* lists[4] = {&h->ev_tick, &h->ev_obs, &h->ev_reset, &h->ev_respawn};
     for (int k = 0; k < 4; k++)
         for (auto& pr : *lists[k]) {
             HIPCHK(hipEventSynchronize(h->ev_pool[pr.second]));
@@ -1753,19 +1208,8 @@ extern "C" int zs_profile_read(zs_handle* h, double* out) {
             HIPCHK(hipEventElapsedTime(&ms, h->ev_pool[pr.first], h->ev_pool[pr.second]));
             tot[k] += ms;
         }
-    out[0] = tot[0];
-    out[1] = (double)h->ev_tick.size();
-    out[2] = tot[1];
-    out[3] = (double)h->ev_obs.size();
-    out[4] = tot[2];
-    out[5] = (double)h->ev_reset.size();
-    out[6] = tot[3];
-    out[7] = (double)h->ev_respawn.size();
-    h->ev_tick.clear();
-    h->ev_obs.clear();
-    h->ev_reset.clear();
-    h->ev_respawn.clear();
-    h->ev_next = 0;
+    for (int k = 0; k < 4; k++) out[2 * k] = tot[k], out[2 * k + 1] = (double)lists[k]->size();
+    prof_clear(h);
     return ZS_OK;
 }
 
@@ -1788,48 +1232,39 @@ extern "C" int zs_describe(zs_handle* h, char* buf, int32_t len) {
     return ZS_OK;
 }
 
-// The actions env's last step executed, in execution order (the shuffled action list of World.step,
-// core.py:76,103-119): per action {slot | kind << 8, target}, kind 1 move (target: the destination,
-// x | y << 16), 2 attack, 3 heal (target: an entity slot, or -1 - obstacle index).  Needs ZS_FLAG_DEATH_LOG.
-extern "C" int zs_action_log(zs_handle* h, int32_t env, int32_t* out_host, int32_t cap, int32_t* n_out, void* stream) {
+// One env's log of its last step (ZS_FLAG_DEATH_LOG): `log` [N][E][words] and its counts.  *n_out: the count clamped
+// to [lo, E]; out_host: the first min(entries, cap) entries, a count n < 0 standing for -1 - n entries.
+static int read_log(zs_handle* h, const int32_t* log, const int32_t* log_n, int words, int lo, int32_t env, int32_t* out_host,
+                    int32_t cap, int32_t* n_out, void* stream) {
     if (!h || !n_out || (cap > 0 && !out_host)) return fail(ZS_EINVAL, "null argument");
-    if (!h->d.alog) return fail(ZS_EINVAL, "the handle was created without ZS_FLAG_DEATH_LOG");
+    if (!log) return fail(ZS_EINVAL, "the handle was created without ZS_FLAG_DEATH_LOG");
     if (env < 0 || env >= h->d.N) return fail(ZS_EINVAL, "env out of range");
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(hipSetDevice(h->device));
     int32_t n = 0;
-    HIPCHK(hipMemcpyAsync(&n, h->d.alog_n + env, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&n, log_n + env, sizeof(int32_t), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
-    // n < 0: a debug raise stopped the step; -1 - n actors before the raising one decided an action
-    n = std::max(-1 - h->d.E, std::min(n, h->d.E));
+    n = std::max(lo, std::min(n, h->d.E));
     const int k = std::min(n < 0 ? -1 - n : n, std::max(0, (int)cap));
     if (k > 0) {
-        HIPCHK(hipMemcpyAsync(out_host, h->d.alog + (size_t)env * h->d.E * 2, sizeof(int32_t) * 2 * k,
-                              hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(out_host, log + (size_t)env * h->d.E * words, sizeof(int32_t) * words * k, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
     }
     *n_out = n;
     return ZS_OK;
 }
 
+// The actions env's last step executed, in execution order (the shuffled action list of World.step,
+// core.py:76,103-119): per action {slot | kind << 8, target}, kind 1 move (target: the destination,
+// x | y << 16), 2 attack, 3 heal (target: an entity slot, or -1 - obstacle index).  Needs ZS_FLAG_DEATH_LOG.
+// n < 0: a debug raise stopped the step; -1 - n actors before the raising one decided an action
+extern "C" int zs_action_log(zs_handle* h, int32_t env, int32_t* out_host, int32_t cap, int32_t* n_out, void* stream) {
+    return read_log(h, h ? h->d.alog : nullptr, h ? h->d.alog_n : nullptr, 2, h ? -1 - h->d.E : 0, env, out_host, cap, n_out, stream);
+}
+
+// The things env's last tick's cleanup removed, in removal order: {slot, serial, x, y, life} each (Dev::dlog)
 extern "C" int zs_death_log(zs_handle* h, int32_t env, int32_t* out_host, int32_t cap, int32_t* n_out, void* stream) {
-    if (!h || !n_out || (cap > 0 && !out_host)) return fail(ZS_EINVAL, "null argument");
-    if (!h->d.dlog) return fail(ZS_EINVAL, "the handle was created without ZS_FLAG_DEATH_LOG");
-    if (env < 0 || env >= h->d.N) return fail(ZS_EINVAL, "env out of range");
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHK(hipSetDevice(h->device));
-    int32_t n = 0;
-    HIPCHK(hipMemcpyAsync(&n, h->d.dlog_n + env, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    n = std::max(0, std::min(n, h->d.E));
-    const int k = std::min(n, std::max(0, (int)cap));
-    if (k > 0) {
-        HIPCHK(hipMemcpyAsync(out_host, h->d.dlog + (size_t)env * h->d.E * 5, sizeof(int32_t) * 5 * k,
-                              hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-    }
-    *n_out = n;
-    return ZS_OK;
+    return read_log(h, h ? h->d.dlog : nullptr, h ? h->d.dlog_n : nullptr, 5, 0, env, out_host, cap, n_out, stream);
 }
 
 // ---------------------------------------------------------------------------
@@ -1890,14 +1325,7 @@ static int host_stage_rng(zs_handle* h, const uint32_t* rng_host) {
     for (size_t e = 0; e < N; e++) {
         const uint32_t* g = rng_host + e * (ZS_MT_N + 1);
         if (g[ZS_MT_N] > ZS_MT_N) return fail(ZS_EINVAL, "MT index out of range (0..624)");
-        uint32_t* r = rings + e * ZS_RING_WORDS;
-        std::memcpy(r, g, sizeof(uint32_t) * ZS_MT_N);
-        for (int k = 0; k < ZS_MT_N; k++) {  // x[k+624] = x[k+397] ^ f(x[k], x[k+1])
-            uint32_t a = r[k], b = r[k + 1], c = r[k + ZS_MT_M];
-            uint32_t y = (a & 0x80000000u) | (b & 0x7fffffffu);
-            r[ZS_MT_N + k] = c ^ (y >> 1) ^ ((y & 1u) ? 0x9908b0dfu : 0u);
-        }
-        st[e] = g[ZS_MT_N] | (0u << 10) | (1u << 11);
+        st[e] = ring_from_state(rings + e * ZS_RING_WORDS, g);
     }
     return ZS_OK;
 }
@@ -1917,9 +1345,7 @@ static int host_call(zs_handle* h, int op, const int32_t* actions_host, const ui
     if (rng_host && (rc = host_stage_rng(h, rng_host))) return rc;
     if (rng_host) {
         const uint32_t* rings = (const uint32_t*)h->d_hin + N * d.A * 3;
-        hipLaunchKernelGGL(k_host_unpack, dim3((unsigned)N), dim3(256), 0, s, h->d, rings, rings + N * ZS_RING_WORDS,
-                           h->d_err);
-        HIPCHK(hipGetLastError());
+        HIPCHK(launch_host_unpack(s, d, rings, rings + N * ZS_RING_WORDS, h->d_err));
     }
     uint8_t *done = h->d_hflags, *trunc = done + N, *rst = trunc + N, *listed = rst + N;
     // the record's error word is this call's alone: an earlier zs_step whose reset work failed leaves the word
@@ -1934,19 +1360,13 @@ static int host_call(zs_handle* h, int op, const int32_t* actions_host, const ui
         HIPCHK(hipMemsetAsync(h->d_hrew, 0, N * L.R * sizeof(double), s));
         rc = queue_reset(h, nullptr, h->d_hobs, s);
     } else {
-        rc = launch_obs(h, h->d_hobs, nullptr, s);
+        rc = launch_obs(h, d, h->d_hobs, nullptr, s);
     }
     if (rc) return rc;
-    hipLaunchKernelGGL(k_host_pack, dim3((unsigned)N), dim3(256), 0, s, h->d, L, (const uint8_t*)h->d_hobs,
-                       (const double*)h->d_hrew, (const uint8_t*)done, (const uint8_t*)trunc,
-                       op == HOST_RESET ? nullptr : (const uint8_t*)rst, h->d_err, h->d_hrec);
-    HIPCHK(hipGetLastError());
+    HIPCHK(launch_host_pack(s, d, L, h->d_hobs, h->d_hrew, done, trunc, op == HOST_RESET ? nullptr : rst, h->d_err, h->d_hrec));
     HIPCHK(hipStreamSynchronize(s));
     std::memcpy(rec_host, h->h_hrec, N * L.words * sizeof(int32_t));
-    const int err = h->h_hrec[ZS_HOST_ERR];
-    if (err == ZS_ENOSPACE) return fail(ZS_ENOSPACE, "Not enough space to spawn players/agents");
-    if (err) return fail(err, "reset failed");
-    return ZS_OK;
+    return reset_result(h->h_hrec[ZS_HOST_ERR]);
 }
 
 extern "C" int zs_host_layout(zs_handle* h, int32_t out[8]) {

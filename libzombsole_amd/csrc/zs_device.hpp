@@ -149,6 +149,21 @@ struct Dev {
     uint32_t* ovf;
 };
 
+// The static observation tables zs_create fills and the observation kernels read (zs_obs.hpp).
+// Dev::scell, the per-cell word: bits 0..15 obstacle index + 1 (0 = none), 16..18 obstacle code, bit 20 objective
+#define SC_OBST_MASK 0xffffu
+#define SC_KIND_SHIFT 16
+#define SC_OBJ_BIT (1u << 20)
+// Dev::opad, the padded table's entry: bits 0..2 the code, bit 3 objective under a map obstacle, bits 8..15 the
+// life; Dev::opk (per obstacle): x | y << 12 | box << 24 | objective-under << 25
+#define OPAD_OBJ 8u
+
+// Diagnostic builds (-DZS_STAMPS, zs_tick.hpp): the per-workgroup phase slots the stamps_* launchers copy out
+#ifdef ZS_STAMPS
+#define ZS_NPHASE 28
+#define ZS_STAMP_WGS 65536
+#endif
+
 // ZS_FLAG_ENV_PARAMS (Dev::flags): per env (initial_zombies, minimum_zombies, max_episode_steps), [3][N] each: the
 // triple of the env's running episode (every reset copies next -> current; the respawn deficit and the TimeLimit read
 // it) and the triple its next reset takes up (zs_env_params_set writes it).  The Dev has no field for them, so the

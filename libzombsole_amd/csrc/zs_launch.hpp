@@ -6,11 +6,18 @@
 //   k_reset.hip   k_reset, k_respawn, k_list_filter
 //   k_mask.hip    k_action_mask (zs_mask.hpp)
 //   k_env_params.hip  k_env_params, k_env_params_get, k_env_params_init, k_env_params_check (ZS_FLAG_ENV_PARAMS)
-//   engine.hip    the C ABI and the small helper kernels (the launches are planned in zs_obs_plan.hpp, zs_step_plan.hpp)
-// Each unit exports plain host functions that launch its kernels; nothing but Dev, the observation
-// plan's ObsKernel (zs_obs_plan.hpp) and plain pointers crosses the units.
+//   k_records.hip  the per-env record movers: k_obs_state_pack, k_obs_state_unpack (zs_obs_state.hpp), k_snapshot,
+//                  k_restore, k_pending_list (zs_snapshot.hpp, zs_record.hpp)
+//   k_state.hip   the small helpers: k_seed, k_gen_actions, k_gen_actions_ctr, k_tail, k_get_state, k_set_state,
+//                 k_host_unpack, k_host_pack, k_init_pending, k_init_obstacles
+//   engine.hip    the handle and the C ABI, host code only (the launches are planned in zs_obs_plan.hpp, zs_step_plan.hpp)
+// Each unit exports plain host functions that launch its kernels, with the launch geometry; nothing but Dev, the
+// observation plan's ObsKernel (zs_obs_plan.hpp), plain structs and plain pointers crosses the units.
 #pragma once
 #include "zs_device.hpp"
+
+struct ObsStateLayout;  // zs_obs_state.hpp
+struct RecTable;        // zs_record.hpp
 
 // one step launch's arguments (k_tick, or k_step when fused)
 struct TickArgs {
@@ -80,3 +87,32 @@ hipError_t launch_env_params_set(hipStream_t s, const Dev& d, int32_t* owner, co
 hipError_t launch_env_params_get(hipStream_t s, const Dev& d, int current, int32_t* out);
 hipError_t launch_env_params_init(hipStream_t s, const Dev& d, int32_t* owner);
 hipError_t launch_env_params_check(hipStream_t s, const Dev& d, uint32_t* out);  // *out = the range word; its PARAM_RANGE bit cleared
+
+// per-env records (k_records.hip).  Observation-state records (zs_obs_state.hpp), rec 16-B aligned: the handle's N
+// envs into rec [N][L.rec_bytes]; records [n] into envs env0 .. env0 + n - 1.  Snapshot records (zs_snapshot.hpp) by
+// the handle's section table T: record k = env idx[k] (null: k); record src[k] of n_records into env dst[k], the
+// written envs' log counts and *list_count zeroed; list = the envs whose needs_reset is set, *count past them
+hipError_t launch_obs_state_pack(hipStream_t s, const Dev& d, const ObsStateLayout& L, void* rec);
+hipError_t launch_obs_state_unpack(hipStream_t s, const Dev& d, const ObsStateLayout& L, int env0, int n, const void* rec);
+hipError_t launch_snapshot(hipStream_t s, const RecTable& T, int N, const int32_t* idx, int n, void* rec);
+hipError_t launch_restore(hipStream_t s, const RecTable& T, const Dev& d, const int32_t* src, const int32_t* dst, int n,
+                          int n_records, const void* rec, int* list_count);
+hipError_t launch_pending_list(hipStream_t s, const int32_t* needs_reset, int N, int* list, int* count);
+
+// Word offsets of a host record's sections (ZS_HOST_* in include/zombsole_mi355x.h, zs_host_layout)
+struct HostLayout {
+    int words, rew, alog, dlog, state, obs, obs_bytes, R;
+};
+
+// the small helpers (k_state.hip)
+hipError_t launch_seed(hipStream_t s, const Dev& d, int env0, int n, const uint64_t* seeds);
+hipError_t launch_gen_actions(hipStream_t s, const Dev& d, uint64_t step, int n_discrete, int32_t* act);
+hipError_t launch_gen_actions_ctr(hipStream_t s, const Dev& d, const uint64_t* ctr, int n_discrete, int32_t* act);
+hipError_t launch_tail(hipStream_t s, const Dev& d);  // the step's tail (Dev::tail_*) when no observation launch ends the step
+hipError_t launch_get_state(hipStream_t s, const Dev& d, int e, int32_t* buf);
+hipError_t launch_set_state(hipStream_t s, const Dev& d, int e, const int32_t* buf, int* err);
+hipError_t launch_host_unpack(hipStream_t s, const Dev& d, const uint32_t* rings, const uint32_t* st, int* err);
+hipError_t launch_host_pack(hipStream_t s, const Dev& d, const HostLayout& L, const uint8_t* obs, const double* rew,
+                            const uint8_t* done, const uint8_t* trunc, const uint8_t* rst, int* err, int32_t* rec);
+hipError_t launch_init_pending(hipStream_t s, const Dev& d, int* list, int* count);
+hipError_t launch_init_obstacles(hipStream_t s, const Dev& d);

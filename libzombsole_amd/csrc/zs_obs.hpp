@@ -21,11 +21,6 @@
 #include "zs_device.hpp"
 #include "zs_obs_plan.hpp"
 
-// static per-cell word: bits 0..15 obstacle index + 1 (0 = none), 16..18 obstacle code, bit 20 objective
-#define SC_OBST_MASK 0xffffu
-#define SC_KIND_SHIFT 16
-#define SC_OBJ_BIT (1u << 20)
-
 typedef unsigned int zs_v4u __attribute__((ext_vector_type(4)));
 typedef unsigned int zs_v2u __attribute__((ext_vector_type(2)));
 typedef int zs_v2i __attribute__((ext_vector_type(2)));
@@ -886,10 +881,7 @@ __global__ void __launch_bounds__(256) k_obs_gather(Dev d, T* out, const uint8_t
 // Per cell that is one LDS read and three slot writes instead of k_obs_lds's five dependent lookups and
 // select chain (C5: ~51 VALU instructions per cell, the kernel VALU-issue-bound at 63 % busy).
 // ---------------------------------------------------------------------------
-// padded table entry (engine.hip: opad): bits 0..2 the code, bit 3 objective under a map obstacle,
-// bits 8..15 the life; opk (per obstacle): x | y << 12 | box << 24 | objective-under << 25
-#define OPAD_OBJ 8u
-// (LDS sizes: patch_static_bytes, patch_enc_bytes, patch_wave_bytes, zs_obs_plan.hpp)
+// (the padded table's entries and opk: OPAD_OBJ, zs_device.hpp; LDS sizes: patch_static_bytes, patch_enc_bytes, patch_wave_bytes, zs_obs_plan.hpp)
 
 // Stage the static tables into the workgroup's LDS (all threads, then a barrier): the padded table,
 // the obstacles' packed cells, and per lane the Box bits of its obstacles lane + 64 i.

@@ -45,7 +45,7 @@
 
 #include "zs_step_plan.hpp"  // ZS_HD, ZS_MT_N, the public header (zs_config)
 
-#define ZS_SNAP_NSCAL 9               // S_NSCAL (zs_device.hpp; engine.hip asserts the two agree)
+#define ZS_SNAP_NSCAL 9               // S_NSCAL (zs_device.hpp; k_records.hip asserts the two agree)
 #define ZS_SNAP_RING (2 * ZS_MT_N)    // ZS_RING_WORDS
 
 // Sections in record order; SNAP_NSEC of them, then the padding.

@@ -26,9 +26,7 @@ enum { K_NONE = 0, K_MOVE = 1, K_ATTACK = 2, K_HEAL = 3, K_DEFER = 4, K_RAISE = 
 // Diagnostic build only (-DZS_STAMPS, never the product .so): lane 0 of every workgroup adds the
 // s_memtime ticks each k_tick phase took into its own slot g_stamp_wg[block][phase] (plain
 // stores, no contended atomics); zs_debug_stamps sums / maxes the slots on the host.
-#ifdef ZS_STAMPS
-#define ZS_NPHASE 28
-#define ZS_STAMP_WGS 65536
+#ifdef ZS_STAMPS  // (ZS_NPHASE phase slots for each of ZS_STAMP_WGS workgroups: zs_device.hpp)
 static __device__ unsigned long long g_stamp_wg[ZS_STAMP_WGS * ZS_NPHASE];
 #define STAMP_DECL unsigned long long _st_prev = 0;
 #define STAMP(k)                                                                          \

@@ -1,5 +1,5 @@
 """Seeds of 2**32 and above: random.seed(int) keys MT19937 with abs(n) in 32-bit little-endian words, two of them
-from 2**32 on.  Both the oracle's mt_seed (oracle/zs_oracle.c) and the engine's k_seed (csrc/engine.hip) take
+from 2**32 on.  Both the oracle's mt_seed (oracle/zs_oracle.c) and the engine's k_seed (csrc/k_state.hip) take
 that branch; every other test seeds below 2**16."""
 import random
 
