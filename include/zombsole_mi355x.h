@@ -127,6 +127,10 @@ extern "C" {
                                 * (initial_zombies, minimum_zombies, max_episode_steps) twice, the triple its next
                                 * reset takes up and the triple of its running episode; both start as the config's
                                 * values, which are the caps.  zs_create refuses it on a viewer handle (ZS_ESTATE) */
+#define ZS_FLAG_EPISODE_STATS 32u /* per-env episode statistics kept on the device (zs_episode_stats_*): every zs_step
+                                   * ends with one more small launch (k_episode_stats).  Without the flag nothing is
+                                   * allocated and nothing is launched.  zs_create refuses it on a viewer handle
+                                   * (ZS_ESTATE) */
 
 /* ---- range flags (zs_overflow) -------------------------------------------
  * The reference's obstacle life is an unbounded Python int that carries over resets
@@ -349,10 +353,13 @@ int zs_obs_state_unpack(zs_handle* h, const void* rec_dev, int32_t rec_bytes, in
  *   spawn serial counter, obstacle-cleanup flag), hp_dirty u32, dead_dirty u32, rngst u32 (MT19937 ring offset
  *   | slot << 10 | next-block-ready << 11), prev_life i32 [A], weapon u8 [E], present u8 [E], order u8 [E],
  *   listed u8 [A], zero padding.  A ZS_FLAG_ENV_PARAMS handle's record holds one section more, env_params
- *   i32 [6] (the current triple, then the next one), after prev_life and before the byte rows.
+ *   i32 [6] (the current triple, then the next one), after prev_life and before the byte rows.  A
+ *   ZS_FLAG_EPISODE_STATS handle's record holds the section ep_run: run_ret f64 [R], run_flags i32, 4 zero bytes;
+ *   8-byte aligned (after 4 zero bytes where needed), behind env_params (if any) and before the byte rows.
  * NOT in a record: the action-stream seed (zs_seed sets it; it belongs to the slot's policy), the death and
  * action logs (a step's outputs: zs_restore empties them for the envs it writes), the handle's sticky
- * ZS_OVF_* word, and zs_step_graph's policy step counter.
+ * ZS_OVF_* word, zs_step_graph's policy step counter, and a ZS_FLAG_EPISODE_STATS handle's last finished episode
+ * and totals (last, last_ret, tot, sum_ret: the slot's own, like the action-stream seed; zs_restore leaves them alone).
  *
  * zs_snapshot_layout: out[0] = rec_bytes; out[1..17] = the byte offsets of the 17 sections in the order
  * above; out[18] = offset of the zero padding; out[19], out[20] = low and high word of the handle's 64-bit
@@ -362,7 +369,8 @@ int zs_obs_state_unpack(zs_handle* h, const void* rec_dev, int32_t rec_bytes, in
  * bots, zombie slots), rules, reward mode, max_episode_steps, initial and minimum zombies and the static
  * tables (obstacle cells and kinds, spawn lists, objective cells, agent weapons, bot types); not the env
  * count, the observation settings, lanes_per_env, the launch overrides or the flags, except ZS_FLAG_ENV_PARAMS
- * (its record is longer), which it covers.
+ * and ZS_FLAG_EPISODE_STATS (their records are longer), which it covers.  The ep_run section's offset is
+ * zs_episode_stats_layout's out[3]; zs_snapshot_layout's out[24] is unchanged.
  *
  * zs_snapshot: record k of rec_dev ([n][rec_bytes], 16-byte aligned) = env env_idx_dev[k] (NULL: env k);
  * duplicates allowed.  Every byte of a record is written (padding: zeros), nothing outside the n records.
@@ -446,6 +454,39 @@ int zs_env_params_set(zs_handle* h, const int32_t* env_idx_dev, int32_t n, const
 int zs_env_params_get(zs_handle* h, int32_t which, int32_t* out_dev, void* stream);
 int zs_env_params_check(zs_handle* h, uint32_t* refused_host, void* stream);
 
+/* ---- per-env episode statistics (ZS_FLAG_EPISODE_STATS) --------------------------------------------------
+ * A flagged handle keeps, per env (R = 1 with ZS_REWARD_SINGLE, num_agents with ZS_REWARD_MULTI):
+ *   running:        run_ret f64 [R], run_flags i32 (bit 0: closed)
+ *   last episode:   last_ret f64 [R], last i32 [8] = {length, outcome, zombie_deaths, deaths, initial_zombies,
+ *                   minimum_zombies, max_episode_steps, serial}; serial is tot[0] after this episode was counted
+ *   totals since zs_create or the last clear: tot u32 [8] = {episodes, won, lost, truncated_agents_dead,
+ *                   truncated_timelimit, sum of length, sum of zombie_deaths, sum of deaths} (sums mod 2^32),
+ *                   sum_ret f64 [R]
+ * Outcome codes (last[1]): 1 won (done and won), 2 lost (done and not won), 3 not done, truncated, no agent alive,
+ * 4 not done, truncated, some agent alive (the TimeLimit); 256 is OR-ed in when done and truncated are both set.
+ * `won` is the rules' own: 2 * alive players >= players for evacuation, else a player alive.
+ * Every zs_step (eager, inside zs_step_graph(_n) for each of its steps, and through zs_host_step) ends with one
+ * launch, after a bound mask launch, that applies per env, in this order: the step was the env's reset: run_ret = 0,
+ * closed = 0; else, if not closed, run_ret[r] = run_ret[r] + rewards[e][r] (one float64 add per step, in step
+ * order); if additionally done | truncated: last_ret = run_ret, last filled (length, zombie_deaths and deaths from the
+ * env's terminal world, the triple the episode ran under), tot bumped, sum_ret[r] += run_ret[r], closed = 1.  A closed
+ * env is not accumulated and not counted again until its next reset (without ZS_FLAG_AUTORESET an ended env keeps
+ * ticking and reporting done).  zs_reset, masked or not, zeroes run_ret and closed of the envs it resets: an
+ * abandoned episode is not counted.  A flagged handle's zs_step accepts reset_dev = NULL like any other.
+ *
+ * zs_episode_stats_layout: out[0] = R, out[1] = words of last (8), out[2] = words of tot (8), out[3] = byte offset
+ * of the ep_run section of the handle's snapshot record, out[4] = its bytes (8 R + 8), out[5..7] = 0.
+ * zs_episode_stats_get: one launch on `stream`; env-major outputs run_ret, last_ret, sum_ret f64 [N][R], last i32
+ * [N][8], tot u32 [N][8].  Any output pointer may be NULL.  The rows of envs whose env_mask_dev byte is 0 are untouched
+ * (NULL: all envs).  Nothing is read back and the host is not synchronised.
+ * zs_episode_stats_clear: zeroes last, last_ret, tot and sum_ret of the masked envs (NULL: all); the running part
+ * stays.  One launch on `stream`.
+ * All three: ZS_ESTATE on a handle created without ZS_FLAG_EPISODE_STATS. */
+int zs_episode_stats_layout(const zs_handle* h, int32_t out[8]);
+int zs_episode_stats_get(zs_handle* h, const uint8_t* env_mask_dev, double* run_ret_dev, double* last_ret_dev,
+                         double* sum_ret_dev, int32_t* last_dev, uint32_t* tot_dev, void* stream);
+int zs_episode_stats_clear(zs_handle* h, const uint8_t* env_mask_dev, void* stream);
+
 /* Diagnostics (not part of the reference surface): when enabled, every k_tick
  * (the step kernel), k_obs (the observation kernel) and k_reset (world rebuild)
  * launch is bracketed by HIP events on its stream.  zs_profile_read synchronizes
@@ -462,7 +503,8 @@ int zs_profile_read(zs_handle* h, double out[8]);
  * "obs_kernel_masked" that of a zs_reset / zs_observe with an env mask, "obs_encoders"
  * ("patched", "select" or "") the encoders of k_obs_ring; "mask_kernel", "mask_grid", "mask_block" the
  * action-mask launch (zs_action_mask) and "mask_bound" whether a buffer is bound; "env_params" whether the handle
- * carries per-env triples (ZS_FLAG_ENV_PARAMS).  Returns ZS_OK. */
+ * carries per-env triples (ZS_FLAG_ENV_PARAMS), "episode_stats" whether it keeps episode statistics
+ * (ZS_FLAG_EPISODE_STATS).  Returns ZS_OK. */
 int zs_describe(zs_handle* h, char* buf, int32_t len);
 /* Diagnostics: out[0], out[1] = the two pending-reset list counts, out[2] = the deferred-respawn
  * count (after everything queued on stream), out[3] = the list parity the next step drains. */

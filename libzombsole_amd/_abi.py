@@ -31,10 +31,15 @@ FLAG_DEBUG = 2
 FLAG_DEATH_LOG = 4  # zs_death_log: the drop-in views' decoration order and removed zombies' final values
 FLAG_VIEWER = 8  # a handle that holds other handles' envs for encoding (zs_obs_state_unpack + zs_observe)
 FLAG_ENV_PARAMS = 16  # per-env (initial_zombies, minimum_zombies, max_episode_steps): zs_env_params_set / _get
+FLAG_EPISODE_STATS = 32  # per-env episode statistics kept on the device: zs_episode_stats_*
 OVF_INT16, OVF_INT32 = 1, 2  # zs_overflow range flags
 OVF_PARAM_RANGE = 4  # zs_env_params_set met an entry it did not apply (env or value out of range)
 ENV_PARAMS = ("initial_zombies", "minimum_zombies", "max_episode_steps")  # a per-env triple, in order
 STATE_HEADER, STATE_ENTITY_WORDS = 16, 8
+# episode statistics (csrc/zs_episode.hpp): the words of `last` and `tot`, the outcome codes of last[1]
+EP_LAST = ("length", "outcome", "zombie_deaths", "deaths", "initial_zombies", "minimum_zombies", "max_episode_steps", "serial")
+EP_TOT = ("episodes", "won", "lost", "truncated_agents_dead", "truncated_timelimit", "length", "zombie_deaths", "deaths")
+EP_WON, EP_LOST, EP_AGENTS_DEAD, EP_TIMELIMIT, EP_DONE_AND_TIMELIMIT = 1, 2, 3, 4, 256
 
 DTYPE_NP = {DTYPE_I32: np.int32, DTYPE_I64: np.int64, DTYPE_I16: np.int16}
 
@@ -90,15 +95,21 @@ def snapshot_section_bytes(E, O, DW, OW, A):
             E, E, E, A)
 
 
-def snapshot_layout(E, O, DW, OW, A, env_params=False):
+def snapshot_layout(E, O, DW, OW, A, env_params=False, episode_R=0):
     """Mirror of snapshot_layout() (csrc/zs_snapshot.hpp): the byte offset of every section of an env's snapshot
     record, "pad" (where the zero padding starts) and "rec_bytes" (a multiple of 16).  env_params: the record of a
-    FLAG_ENV_PARAMS handle, with "env_params" (six int32: the current triple, then the next) before the byte rows."""
+    FLAG_ENV_PARAMS handle, with "env_params" (six int32: the current triple, then the next) before the byte rows.
+    episode_R > 0: the record of a FLAG_EPISODE_STATS handle with that many reward slots per env, with "ep_run" (8-byte
+    aligned: run_ret float64 [R], run_flags int32, 4 zero bytes) behind env_params and "ep_bytes"."""
     L, o = {}, 0
     for name, nbytes in zip(SNAPSHOT_SECTIONS, snapshot_section_bytes(E, O, DW, OW, A)):
         if env_params and name == "weapon":
             L["env_params"] = o
             o += 4 * 6
+        if episode_R and name == "weapon":
+            o += o & 4
+            L["ep_run"], L["ep_bytes"] = o, 8 * episode_R + 8
+            o += 8 * episode_R + 8
         L[name] = o
         o += nbytes
     L["pad"] = o
@@ -140,6 +151,8 @@ def snapshot_fingerprint(cfg):
     h = _fp_table(h, cfg.bot_types[:cfg.num_bots])
     if cfg.flags & FLAG_ENV_PARAMS:  # the longer record: flagged and unflagged handles do not exchange records
         h = _fp_add(h, FLAG_ENV_PARAMS)
+    if cfg.flags & FLAG_EPISODE_STATS:
+        h = _fp_add(h, FLAG_EPISODE_STATS)
     return h
 
 
@@ -244,7 +257,8 @@ class ConfigBuilder(object):
 
     def __init__(self, num_envs, map_, rules, agent_weapons, agent_codes, bot_types, initial_zombies,
                  minimum_zombies, reward_mode, obs_scope, obs_encoding, obs_width, obs_dtype,
-                 max_episode_steps=0, autoreset=True, lanes_per_env=0, debug=False, viewer=False, env_params=False):
+                 max_episode_steps=0, autoreset=True, lanes_per_env=0, debug=False, viewer=False, env_params=False,
+                 episode_stats=False):
         m = map_ if isinstance(map_, Map) else load_map(map_)
         self.map = m
 
@@ -270,7 +284,8 @@ class ConfigBuilder(object):
                              int(reward_mode), int(obs_scope), int(obs_encoding), int(obs_width),
                              int(obs_dtype), int(max_episode_steps),
                              (FLAG_AUTORESET if autoreset else 0) | (FLAG_DEBUG if debug else 0) |
-                             (FLAG_VIEWER if viewer else 0) | (FLAG_ENV_PARAMS if env_params else 0),
+                             (FLAG_VIEWER if viewer else 0) | (FLAG_ENV_PARAMS if env_params else 0) |
+                             (FLAG_EPISODE_STATS if episode_stats else 0),
                              int(lanes_per_env))
         self._launch = None
 
@@ -317,7 +332,8 @@ class ConfigBuilder(object):
         c, m = self.cfg, self.cfg.map
         E = c.num_agents + c.num_bots + max(c.initial_zombies, c.minimum_zombies)
         L = snapshot_layout(E, m.n_obstacles, (m.width * m.height + 31) // 32, (m.n_obstacles + 31) // 32, c.num_agents,
-                            bool(c.flags & FLAG_ENV_PARAMS))
+                            bool(c.flags & FLAG_ENV_PARAMS),
+                            (c.num_agents if c.reward_mode == REWARD_MULTI else 1) if c.flags & FLAG_EPISODE_STATS else 0)
         L["fingerprint"] = snapshot_fingerprint(c)
         return L
 
@@ -347,7 +363,7 @@ class ConfigBuilder(object):
 def single_env_config(num_envs, rules_name, player_names, map_name, agent_id, initial_zombies=0,
                       minimum_zombies=0, observation_scope="world", observation_position_encoding="simple",
                       agent_weapon="rifle", max_episode_steps=0, obs_dtype=DTYPE_I32, autoreset=True,
-                      lanes_per_env=0, debug=False, viewer=False, env_params=False):
+                      lanes_per_env=0, debug=False, viewer=False, env_params=False, episode_stats=False):
     """zs_config for the ZombsoleGymEnv surface (gym_env.py:49-83): one agent + bots."""
     m = load_map(map_name)
     rules = rules_id(rules_name)
@@ -357,14 +373,14 @@ def single_env_config(num_envs, rules_name, player_names, map_name, agent_id, in
     enc = parse_encoding(observation_position_encoding)
     return ConfigBuilder(num_envs, m, rules, weapons, [agent_code(agent_id)], bots, initial_zombies,
                          minimum_zombies, REWARD_SINGLE, scope, enc, width, obs_dtype, max_episode_steps,
-                         autoreset, lanes_per_env, debug, viewer, env_params)
+                         autoreset, lanes_per_env, debug, viewer, env_params, episode_stats)
 
 
 def multi_env_config(num_envs, rules_name, player_names, map_name, agent_ids, initial_zombies=0,
                      minimum_zombies=0, observation_surroundings_width=21,
                      observation_position_encoding_style="channels", agent_weapons="rifle",
                      max_episode_steps=0, obs_dtype=DTYPE_I64, autoreset=True, lanes_per_env=0, debug=False,
-                     viewer=False, env_params=False):
+                     viewer=False, env_params=False, episode_stats=False):
     """zs_config for the MultiagentZombsoleEnv surface (gym/multiagent_env.py:25-78)."""
     w = int(observation_surroundings_width)
     if (w % 2 == 0) or (w <= 1):
@@ -378,4 +394,4 @@ def multi_env_config(num_envs, rules_name, player_names, map_name, agent_ids, in
     weapons = [weapon_id(n) for n in names]
     return ConfigBuilder(num_envs, m, rules, weapons, [agent_code(a) for a in ids], bots, initial_zombies,
                          minimum_zombies, REWARD_MULTI, OBS_SURROUNDINGS, enc, w, obs_dtype,
-                         max_episode_steps, autoreset, lanes_per_env, debug, viewer, env_params)
+                         max_episode_steps, autoreset, lanes_per_env, debug, viewer, env_params, episode_stats)

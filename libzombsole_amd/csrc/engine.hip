@@ -8,7 +8,8 @@
 // (zs_mask.hpp) when a mask buffer is bound.  zs_step_graph replays a step as a hipGraph.  The small helpers behind the
 // ABI (seeding, the policy stream, the state views, the drop-ins' per-call records) are k_state.hip's; the per-env
 // record movers (observation-state records, zs_obs_state.hpp; snapshot records, zs_snapshot.hpp and zs_record.hpp) are
-// k_records.hip's; k_env_params.hip scatters per-env zombie counts and time limits (ZS_FLAG_ENV_PARAMS).
+// k_records.hip's; k_env_params.hip scatters per-env zombie counts and time limits (ZS_FLAG_ENV_PARAMS); a
+// ZS_FLAG_EPISODE_STATS handle's step ends with k_episode_stats (k_episode.hip, zs_episode.hpp).
 //
 // Semantics follow the reference exactly (parity: tests/); every sqrt range
 // test of the reference is replaced by its exact integer d^2 equivalent.
@@ -25,6 +26,7 @@
 #include "zs_snapshot.hpp"
 #include "zs_record.hpp"
 #include "zs_mask.hpp"  // the mask launch's geometry (zs_describe); the kernel is k_mask.hip's
+#include "zs_episode.hpp"  // the running part's columns (ZS_EP_RUN_COLS); the kernels are k_episode.hip's
 
 // ===========================================================================
 // host side: C ABI
@@ -89,6 +91,10 @@ struct zs_handle {
     uint64_t snap_fp = 0;  // snapshot_fingerprint() of the config (zs_snapshot.hpp)
     int32_t* d_envp_owner = nullptr;  // ZS_FLAG_ENV_PARAMS: zs_env_params_set's scratch, int32 [N], -1 between calls
     void* mask_bound = nullptr;  // zs_action_mask_bind: every zs_step ends with a mask launch into it
+    // ZS_FLAG_EPISODE_STATS: the statistics' arrays (k_episode.hip's argument; ep.run null without the flag) and the
+    // [N] byte row the tick writes its reset flags to when the caller passes no reset_dev
+    EpisodeArgs ep{};
+    uint8_t* d_ep_reset = nullptr;
     // the drop-ins' per-call path (zs_host_*), set up by its first call: one pinned, device-mapped input
     // block (actions, then the `random` state as rings + st words) the kernels read in place, one pinned,
     // device-mapped record block k_host_pack writes in place, one synchronisation per call
@@ -464,6 +470,20 @@ static int create_env_arrays(zs_handle* h, const zs_map_desc& m) {
     if (d.flags & ZS_FLAG_ENV_PARAMS) {
         TRY(dalloc(h, &h->d_envp_owner, N + 1));  // and, behind the row, zs_env_params_check's word
     }
+    if (d.flags & ZS_FLAG_EPISODE_STATS) {
+        EpisodeArgs& a = h->ep;
+        const size_t R = d.reward_mode == ZS_REWARD_SINGLE ? 1 : d.A;
+        a.N = d.N, a.R = (int)R, a.A = d.A, a.P = d.P, a.E = d.E, a.rules = d.rules;
+        a.initial_zombies = d.initial_zombies, a.minimum_zombies = d.minimum_zombies, a.max_steps = d.max_steps;
+        a.envp = (d.flags & ZS_FLAG_ENV_PARAMS) ? envp_cur(d) : nullptr;
+        a.scal = d.scal, a.life = d.life;
+        TRY(dalloc(h, &a.run, (size_t)ZS_EP_RUN_COLS(R) * N));
+        TRY(dalloc(h, &a.last_ret, R * N));
+        TRY(dalloc(h, &a.sum_ret, R * N));
+        TRY(dalloc(h, &a.last, (size_t)ZS_EP_LAST * N));
+        TRY(dalloc(h, &a.tot, (size_t)ZS_EP_TOT * N));
+        TRY(dalloc(h, &h->d_ep_reset, N));
+    }
     return ZS_OK;
 }
 
@@ -518,6 +538,8 @@ extern "C" int zs_create(const zs_config* cfg, int device, zs_handle** out) {
     if (rc) return rc;
     if ((cfg->flags & ZS_FLAG_ENV_PARAMS) && (cfg->flags & ZS_FLAG_VIEWER))  // nothing resets or steps a viewer's envs
         return fail(ZS_ESTATE, "zs_create: ZS_FLAG_ENV_PARAMS: not on a viewer handle (ZS_FLAG_VIEWER)");
+    if ((cfg->flags & ZS_FLAG_EPISODE_STATS) && (cfg->flags & ZS_FLAG_VIEWER))
+        return fail(ZS_ESTATE, "zs_create: ZS_FLAG_EPISODE_STATS: not on a viewer handle (ZS_FLAG_VIEWER)");
     HIPCHK(hipSetDevice(device));
     HandleOwner owner{new zs_handle()};
     zs_handle* h = owner.h;
@@ -688,6 +710,8 @@ static int queue_reset(zs_handle* h, const uint8_t* env_mask_dev, void* obs_dev,
             h->rpar = q;
         }
     }
+    // ZS_FLAG_EPISODE_STATS: the reset envs' running return starts over; an abandoned episode is not counted
+    if (h->ep.run) HIPCHK(launch_episode_clear(s, h->ep, env_mask_dev, 1));
     return launch_obs(h, h->d, obs_dev, env_mask_dev, s);
 }
 
@@ -718,6 +742,9 @@ extern "C" int zs_step(zs_handle* h, const int32_t* actions_dev, void* obs_dev, 
     NOT_ON_VIEWER(h, "zs_step");
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(hipSetDevice(h->device));
+    // ZS_FLAG_EPISODE_STATS: the update rule reads the tick's reset flags, so a caller that wants none gets the
+    // handle's own row (one row whatever the caller's buffers: the step graphs stay keyed on the caller's pointers)
+    if (h->ep.run && !reset_dev) reset_dev = h->d_ep_reset;
     // 1) rebuild the envs that ended at the previous call (list[p]); fused into the tick launch
     //    when the LDS images allow, else a k_reset launch first
     int q = 1 - h->rpar, rc = ZS_OK;
@@ -793,6 +820,12 @@ extern "C" int zs_step(zs_handle* h, const int32_t* actions_dev, void* obs_dev, 
     if (h->mask_bound) {
         const hipError_t me = launch_action_mask(s, d, nullptr, h->mask_bound);
         if (me != hipSuccess) return fail(ZS_EHIP, std::string("k_action_mask: ") + hipGetErrorString(me));
+    }
+    // 5) ZS_FLAG_EPISODE_STATS: the step's rewards and flags into the running returns, a finished episode latched
+    //    and counted (the terminal world stays until the next call's reset work)
+    if (h->ep.run) {
+        const hipError_t ee = launch_episode_stats(s, h->ep, rewards_dev, done_dev, trunc_dev, reset_dev);
+        if (ee != hipSuccess) return fail(ZS_EHIP, std::string("k_episode_stats: ") + hipGetErrorString(ee));
     }
     return ZS_OK;
 }
@@ -1027,7 +1060,7 @@ extern "C" int zs_obs_state_unpack(zs_handle* h, const void* rec_dev, int32_t re
 // ---------------------------------------------------------------------------
 static SnapshotLayout handle_snapshot_layout(const zs_handle* h) {
     const Dev& d = h->d;
-    return snapshot_layout(d.E, d.O, d.DW, d.OW, d.A, (d.flags & ZS_FLAG_ENV_PARAMS) != 0);
+    return snapshot_layout(d.E, d.O, d.DW, d.OW, d.A, (d.flags & ZS_FLAG_ENV_PARAMS) != 0, h->ep.run ? h->ep.R : 0);
 }
 
 // the engine-side table of a snapshot record (zs_record.hpp): the handle's arrays in record order
@@ -1036,7 +1069,8 @@ static RecTable snapshot_table(const zs_handle* h) {
     void* const base[SNAP_NSEC] = {d.ring, d.dead, d.obst_hp, d.obst_present, d.obst_nonpos, d.pos, d.life, d.serial,
                                    d.scal, d.hp_dirty, d.dead_dirty, d.rngst, d.prev_life,
                                    d.weapon, d.present, d.order, d.listed};
-    return snapshot_rec_table(base, d.E, d.O, d.DW, d.OW, d.A, (size_t)d.N, (d.flags & ZS_FLAG_ENV_PARAMS) ? envp_cur(d) : nullptr);
+    return snapshot_rec_table(base, d.E, d.O, d.DW, d.OW, d.A, (size_t)d.N, (d.flags & ZS_FLAG_ENV_PARAMS) ? envp_cur(d) : nullptr,
+                              h->ep.run, h->ep.R);
 }
 
 extern "C" int zs_snapshot_layout(const zs_handle* h, int32_t out[24]) {
@@ -1135,6 +1169,45 @@ extern "C" int zs_env_params_get(zs_handle* h, int32_t which, int32_t* out_dev, 
 }
 
 // ---------------------------------------------------------------------------
+// per-env episode statistics (ZS_FLAG_EPISODE_STATS; k_episode.hip): asynchronous, nothing read back
+// ---------------------------------------------------------------------------
+static int episode_stats_refused(const zs_handle* h, const char* call) {
+    if (h->ep.run) return ZS_OK;
+    return fail(ZS_ESTATE, std::string(call) + ": the handle was created without ZS_FLAG_EPISODE_STATS");
+}
+
+extern "C" int zs_episode_stats_layout(const zs_handle* h, int32_t out[8]) {
+    if (!h || !out) return fail(ZS_EINVAL, "null argument");
+    int rc = episode_stats_refused(h, "zs_episode_stats_layout");
+    if (rc) return rc;
+    const SnapshotLayout L = handle_snapshot_layout(h);
+    const int32_t v[8] = {h->ep.R, ZS_EP_LAST, ZS_EP_TOT, L.ep_run, L.ep_bytes, 0, 0, 0};
+    std::memcpy(out, v, sizeof(v));
+    return ZS_OK;
+}
+
+extern "C" int zs_episode_stats_get(zs_handle* h, const uint8_t* env_mask_dev, double* run_ret_dev, double* last_ret_dev,
+                                    double* sum_ret_dev, int32_t* last_dev, uint32_t* tot_dev, void* stream) {
+    if (!h) return fail(ZS_EINVAL, "null handle");
+    int rc = episode_stats_refused(h, "zs_episode_stats_get");
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(launch_episode_get(s, h->ep, env_mask_dev, run_ret_dev, last_ret_dev, sum_ret_dev, last_dev, tot_dev));
+    return ZS_OK;
+}
+
+extern "C" int zs_episode_stats_clear(zs_handle* h, const uint8_t* env_mask_dev, void* stream) {
+    if (!h) return fail(ZS_EINVAL, "null handle");
+    int rc = episode_stats_refused(h, "zs_episode_stats_clear");
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(launch_episode_clear(s, h->ep, env_mask_dev, 0));
+    return ZS_OK;
+}
+
+// ---------------------------------------------------------------------------
 // An env's MT19937 stream in CPython's random.getstate() form: state[0..623] = the raw
 // block being consumed, state[624] = index of the next word (0..624; 624 = exhausted, the
 // next draw twists).  The single-env wrappers move the process-global `random` state in
@@ -1223,12 +1296,12 @@ extern "C" int zs_describe(zs_handle* h, char* buf, int32_t len) {
              "\"step_wgs_per_cu\": %d, \"rng_window\": %d, \"obs_kernel\": \"%s\", \"reset_side_stream\": %d, "
              "\"reset_lds\": %d, \"respawn\": \"%s\", \"tick_waves\": %d, \"rng_step\": %d, \"par_exec\": %d, "
              "\"obs_kernel_masked\": \"%s\", \"obs_encoders\": \"%s\", \"mask_kernel\": \"k_action_mask\", "
-             "\"mask_grid\": %u, \"mask_block\": %d, \"mask_bound\": %d, \"env_params\": %d}",
+             "\"mask_grid\": %u, \"mask_block\": %d, \"mask_bound\": %d, \"env_params\": %d, \"episode_stats\": %d}",
              d.N, d.E, p.G, p.fused ? "k_step" : "k_tick", p.lds, p.resident, p.rw_cap,
              d.fobs ? "step launch" : obs_kernel_name(kf.kind), h->reset_side,
              p.reset_lds, p.defer_respawn ? "k_respawn" : "tick", p.tick_waves, p.rw_step,
              d.par_exec, obs_kernel_name(h->obs.masked.kind), obs_encoders_name(kf), zs_mask_grid(d.N), ZS_MASK_BLOCK,
-             h->mask_bound ? 1 : 0, (d.flags & ZS_FLAG_ENV_PARAMS) ? 1 : 0);
+             h->mask_bound ? 1 : 0, (d.flags & ZS_FLAG_ENV_PARAMS) ? 1 : 0, h->ep.run ? 1 : 0);
     return ZS_OK;
 }
 

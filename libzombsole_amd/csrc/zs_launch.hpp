@@ -6,6 +6,7 @@
 //   k_reset.hip   k_reset, k_respawn, k_list_filter
 //   k_mask.hip    k_action_mask (zs_mask.hpp)
 //   k_env_params.hip  k_env_params, k_env_params_get, k_env_params_init, k_env_params_check (ZS_FLAG_ENV_PARAMS)
+//   k_episode.hip  k_episode_stats, k_episode_get, k_episode_clear (ZS_FLAG_EPISODE_STATS; zs_episode.hpp)
 //   k_records.hip  the per-env record movers: k_obs_state_pack, k_obs_state_unpack (zs_obs_state.hpp), k_snapshot,
 //                  k_restore, k_pending_list (zs_snapshot.hpp, zs_record.hpp)
 //   k_state.hip   the small helpers: k_seed, k_gen_actions, k_gen_actions_ctr, k_tail, k_get_state, k_set_state,
@@ -87,6 +88,29 @@ hipError_t launch_env_params_set(hipStream_t s, const Dev& d, int32_t* owner, co
 hipError_t launch_env_params_get(hipStream_t s, const Dev& d, int current, int32_t* out);
 hipError_t launch_env_params_init(hipStream_t s, const Dev& d, int32_t* owner);
 hipError_t launch_env_params_check(hipStream_t s, const Dev& d, uint32_t* out);  // *out = the range word; its PARAM_RANGE bit cleared
+
+// per-env episode statistics (k_episode.hip; ZS_FLAG_EPISODE_STATS handles).  The statistics' arrays are the handle's
+// own and reach these kernels alone, as their argument: the Dev has no field for them.
+struct EpisodeArgs {
+    int N, R, A, P, E, rules;
+    int initial_zombies, minimum_zombies, max_steps;  // the config's triple (envp null)
+    const int32_t* envp;  // ZS_FLAG_ENV_PARAMS: the running episodes' triples, [3][N] (envp_cur()), else null
+    const int32_t* scal;  // Dev::scal
+    const int32_t* life;  // Dev::life
+    uint32_t* run;        // [ZS_EP_RUN_COLS(R)][N] (zs_episode.hpp)
+    double* last_ret;     // [R][N]
+    double* sum_ret;      // [R][N]
+    int32_t* last;        // [8][N]
+    uint32_t* tot;        // [8][N]
+};
+// the step's last launch: the update rule over the step's outputs (was_reset: the tick's reset_out, never null);
+// the columns into env-major tensors (any null) for the envs whose mask byte is nonzero (null: all); the masked envs'
+// running part (running != 0) or last episode and totals, zeroed
+hipError_t launch_episode_stats(hipStream_t s, const EpisodeArgs& a, const double* rew, const uint8_t* done, const uint8_t* trunc,
+                                const uint8_t* was_reset);
+hipError_t launch_episode_get(hipStream_t s, const EpisodeArgs& a, const uint8_t* mask, double* run_ret, double* last_ret,
+                              double* sum_ret, int32_t* last, uint32_t* tot);
+hipError_t launch_episode_clear(hipStream_t s, const EpisodeArgs& a, const uint8_t* mask, int running);
 
 // per-env records (k_records.hip).  Observation-state records (zs_obs_state.hpp), rec 16-B aligned: the handle's N
 // envs into rec [N][L.rec_bytes]; records [n] into envs env0 .. env0 + n - 1.  Snapshot records (zs_snapshot.hpp) by

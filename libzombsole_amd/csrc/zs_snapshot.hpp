@@ -28,6 +28,10 @@
 //     prev_life    i32 [A]              the reward tracker's previous life per agent
 //   on a ZS_FLAG_ENV_PARAMS handle only:
 //     env_params   i32 [6]              the running episode's (initial, minimum, max_steps), then the next reset's
+//   on a ZS_FLAG_EPISODE_STATS handle only, 8-byte aligned (4 zero bytes ahead of it where the sections before it end
+//   at an odd dword):
+//     ep_run       f64 [R], i32, 4 zero bytes   the running episode's return (R = 1 on the single surface, A on the
+//                                       multi surface) and run_flags (zs_episode.hpp)
 //   the byte rows:
 //     weapon, present, order  u8 [E] each
 //     listed       u8 [A]               ([a][N] columns in the engine)
@@ -39,7 +43,10 @@
 //   * the death and action logs (ZS_FLAG_DEATH_LOG): they are a step's outputs; zs_restore zeroes the counts
 //     (dlog_n, alog_n) of the envs it writes when the handle keeps logs;
 //   * the handle's sticky ZS_OVF_* word (zs_overflow);
-//   * the policy step counter of zs_step_graph.
+//   * the policy step counter of zs_step_graph;
+//   * the last finished episode and the totals of a ZS_FLAG_EPISODE_STATS handle (last, last_ret, tot, sum_ret): they
+//     are the slot's own, like the action-stream seed, and zs_restore leaves them alone.  Only the running part
+//     (ep_run) belongs to an env.
 #pragma once
 #include <stdint.h>
 
@@ -63,19 +70,25 @@ struct SnapshotLayout {
     int off[SNAP_NSEC + 1];  // byte offset of every section; off[SNAP_NSEC] = where the zero padding starts
     int rec_bytes;           // a multiple of 16
     int envp;                // byte offset of the env_params section (ZS_FLAG_ENV_PARAMS handles), else 0
+    int ep_run;              // byte offset of the ep_run section (ZS_FLAG_EPISODE_STATS handles), 8-byte aligned, else 0
+    int ep_bytes;            // its bytes, 8 R + 8, else 0
+    int ep_gap;              // zero bytes ahead of it (0 or 4)
 };
 
 // env_params: the record of a ZS_FLAG_ENV_PARAMS handle, which holds one section more, env_params i32 [ZS_SNAP_ENVP]
 // (the engine's [6][N] columns), after prev_life, the last of the 4-byte sections, and before the byte rows
-ZS_HD inline SnapshotLayout snapshot_layout(int E, int O, int DW, int OW, int A, bool env_params = false) {
+// ep_R: the record of a ZS_FLAG_EPISODE_STATS handle with R reward slots per env (0: none), which holds ep_run behind
+// env_params (if any) and before the byte rows
+ZS_HD inline SnapshotLayout snapshot_layout(int E, int O, int DW, int OW, int A, bool env_params = false, int ep_R = 0) {
     const int bytes[SNAP_NSEC] = {4 * ZS_SNAP_RING, 4 * DW, 4 * O, 4 * OW, 4 * OW, 4 * E, 4 * E, 4 * E,
                                   4 * ZS_SNAP_NSCAL, 4, 4, 4, 4 * A,
                                   E, E, E, A};
     SnapshotLayout L;
-    L.envp = 0;
+    L.envp = L.ep_run = L.ep_bytes = L.ep_gap = 0;
     int o = 0;
     for (int s = 0; s < SNAP_NSEC; s++) {
         if (s == SNAP_NWORD && env_params) L.envp = o, o += 4 * ZS_SNAP_ENVP;
+        if (s == SNAP_NWORD && ep_R > 0) L.ep_gap = o & 4, L.ep_run = o + L.ep_gap, L.ep_bytes = 8 * ep_R + 8, o = L.ep_run + L.ep_bytes;
         L.off[s] = o, o += bytes[s];
     }
     L.off[SNAP_NSEC] = o;
@@ -89,8 +102,8 @@ ZS_HD inline SnapshotLayout snapshot_layout(int E, int O, int DW, int OW, int A,
 // zombies, and the static tables: obstacle cells and kinds, player and zombie spawn lists, objective cells, agent
 // weapons, bot types (each with its length).  Deliberately not covered: the env count, the observation settings
 // (scope, encoding, width, dtype, agent codes), lanes_per_env, the launch overrides and the flags, but for
-// ZS_FLAG_ENV_PARAMS: a handle with it has the longer record, so the flag is hashed in (last, and only when set: the
-// fingerprints of handles without it are what they were).
+// ZS_FLAG_ENV_PARAMS and ZS_FLAG_EPISODE_STATS: a handle with either has a longer record, so the flag is hashed in
+// (last, in that order, and only when set: the fingerprints of handles without them are what they were).
 // ---------------------------------------------------------------------------
 inline uint64_t snapshot_fp_add(uint64_t h, uint64_t v) {  // splitmix64's finaliser over the running value
     uint64_t z = (h ^ v) + 0x9E3779B97F4A7C15ull;
@@ -122,5 +135,6 @@ inline uint64_t snapshot_fingerprint(const zs_config* c) {
     h = snapshot_fp_table(h, c->agent_weapons, c->num_agents);
     h = snapshot_fp_table(h, c->bot_types, c->num_bots);
     if (c->flags & ZS_FLAG_ENV_PARAMS) h = snapshot_fp_add(h, (uint64_t)ZS_FLAG_ENV_PARAMS);
+    if (c->flags & ZS_FLAG_EPISODE_STATS) h = snapshot_fp_add(h, (uint64_t)ZS_FLAG_EPISODE_STATS);
     return h;
 }

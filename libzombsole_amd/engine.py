@@ -19,7 +19,8 @@ SYMBOLS = ["zs_last_error", "zs_create", "zs_destroy", "zs_obs_shape", "zs_seed"
            "zs_obs_state_layout", "zs_obs_state_pack", "zs_obs_state_unpack",
            "zs_snapshot_layout", "zs_snapshot", "zs_restore",
            "zs_action_mask", "zs_action_mask_bind",
-           "zs_env_params_set", "zs_env_params_get", "zs_env_params_check"]
+           "zs_env_params_set", "zs_env_params_get", "zs_env_params_check",
+           "zs_episode_stats_layout", "zs_episode_stats_get", "zs_episode_stats_clear"]
 
 _lib = None
 
@@ -85,6 +86,9 @@ def load_library(path=None):
     L.zs_env_params_set.argtypes = [vp, vp, i32, vp, vp]
     L.zs_env_params_get.argtypes = [vp, i32, vp, vp]
     L.zs_env_params_check.argtypes = [vp, C.POINTER(C.c_uint32), vp]
+    L.zs_episode_stats_layout.argtypes = [vp, C.POINTER(i32)]
+    L.zs_episode_stats_get.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
+    L.zs_episode_stats_clear.argtypes = [vp, vp, vp]
     for s in SYMBOLS:
         if s != "zs_last_error":
             getattr(L, s).restype = C.c_int
@@ -477,6 +481,48 @@ class Engine(object):
         if rc:
             _raise(self.L, rc, "zs_env_params_get")
         return o
+
+    # -- per-env episode statistics (zs_episode_stats_*; a config with FLAG_EPISODE_STATS) -------------------------
+    def episode_stats_layout(self):
+        """zs_episode_stats_layout as a dict: "R" (reward slots per env), "last_words", "tot_words" (8 each), and the
+        byte offset "ep_run" and size "ep_bytes" of the running part's section of the handle's snapshot record."""
+        if getattr(self, "_epl", None) is None:
+            out = (C.c_int32 * 8)()
+            rc = self.L.zs_episode_stats_layout(self.h, out)
+            if rc:
+                _raise(self.L, rc, "zs_episode_stats_layout")
+            self._epl = dict(zip(("R", "last_words", "tot_words", "ep_run", "ep_bytes"), [int(v) for v in out]))
+        return self._epl
+
+    def episode_stats(self, mask=None, out=None):
+        """The episode statistics as a dict of five device tensors (zs_episode_stats_get, one launch, no
+        synchronisation): "run_ret", "last_ret", "sum_ret" float64 [N, R], "last" int32 [N, 8] (_abi.EP_LAST) and "tot"
+        (_abi.EP_TOT; uint32 counters in an int32 tensor, read with & 0xffffffff).  Envs where the uint8 device tensor
+        `mask` is zero keep their rows: zero in the tensors this call allocates, untouched in `out` (a dict of the
+        same five contiguous tensors, any of them None to skip it)."""
+        t = self.torch
+        R = self.episode_stats_layout()["R"]
+        shapes = {"run_ret": (t.float64, R), "last_ret": (t.float64, R), "sum_ret": (t.float64, R), "last": (t.int32, 8),
+                  "tot": (t.int32, 8)}
+        if out is None:
+            out = {k: t.zeros((self.N, w), dtype=dt, device=self.device) for k, (dt, w) in shapes.items()}
+        for k, (dt, w) in shapes.items():
+            o = out.get(k)
+            if o is not None and (o.dtype != dt or tuple(o.shape) != (self.N, w) or not o.is_contiguous() or
+                                  o.device != self.device):
+                raise ValueError("episode_stats: %s is a contiguous %s tensor [%d, %d] on %s" % (k, dt, self.N, w, self.device))
+        rc = self.L.zs_episode_stats_get(self.h, _ptr(mask), _ptr(out.get("run_ret")), _ptr(out.get("last_ret")),
+                                         _ptr(out.get("sum_ret")), _ptr(out.get("last")), _ptr(out.get("tot")), self._stream())
+        if rc:
+            _raise(self.L, rc, "zs_episode_stats_get")
+        return out
+
+    def clear_episode_stats(self, mask=None):
+        """Zero the last finished episode and the totals of every env (or where the uint8 device tensor `mask` is
+        nonzero); the running returns stay (zs_episode_stats_clear)."""
+        rc = self.L.zs_episode_stats_clear(self.h, _ptr(mask), self._stream())
+        if rc:
+            _raise(self.L, rc, "zs_episode_stats_clear")
 
     def gen_actions(self, step, n_discrete, out=None):
         o = self.actions if out is None else out

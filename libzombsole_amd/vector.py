@@ -67,19 +67,19 @@ class BatchedZombsole(object):
                  observation_scope="world", observation_position_encoding="simple", agent_weapon="rifle",
                  observation_surroundings_width=21, observation_position_encoding_style="channels",
                  agent_weapons="rifle", obs_dtype=None, autoreset=True, device=None, lanes_per_env=0,
-                 action_masks=False, env_params=False):
+                 action_masks=False, env_params=False, episode_stats=False):
         if surface == "single":
             b = _abi.single_env_config(num_envs, rules_name, player_names, map_name, agent_id, initial_zombies,
                                        minimum_zombies, observation_scope, observation_position_encoding,
                                        agent_weapon, max_episode_steps,
                                        _abi.DTYPE_I32 if obs_dtype is None else obs_dtype, autoreset, lanes_per_env,
-                                       env_params=env_params)
+                                       env_params=env_params, episode_stats=episode_stats)
         elif surface == "multi":
             b = _abi.multi_env_config(num_envs, rules_name, player_names, map_name, agent_ids, initial_zombies,
                                       minimum_zombies, observation_surroundings_width,
                                       observation_position_encoding_style, agent_weapons, max_episode_steps,
                                       _abi.DTYPE_I64 if obs_dtype is None else obs_dtype, autoreset, lanes_per_env,
-                                      env_params=env_params)
+                                      env_params=env_params, episode_stats=episode_stats)
         else:
             raise ValueError("surface must be 'single' or 'multi'")
         self.surface = surface
@@ -120,6 +120,30 @@ class BatchedZombsole(object):
     def env_params_current(self):
         """int32 [N, 3]: the triple of every env's running episode."""
         return self.engine.env_params(current=True)
+
+    # -- episode statistics (episode_stats=True): returns, lengths and outcomes per env, kept on the device ---------
+    def episode_stats(self, mask=None):
+        """Engine.episode_stats: a dict of "run_ret", "last_ret", "sum_ret" (float64 [N, R]), "last" and "tot" (int32
+        [N, 8]; _abi.EP_LAST, _abi.EP_TOT) on the device.  Correct at any number of steps per launch."""
+        return self.engine.episode_stats(mask)
+
+    def clear_episode_stats(self, mask=None):
+        """Zero the last finished episode and the totals of the masked envs (default: all); running returns stay."""
+        self.engine.clear_episode_stats(mask)
+
+    def episode_totals(self, groups=None, n_groups=1):
+        """The totals summed over groups of envs (e.g. curriculum levels): `groups` int64 [N] with values in
+        [0, n_groups) (default: one group).  Returns {"tot": int64 [n_groups, 8], "sum_ret": float64 [n_groups, R]}, a
+        torch.index_add_ of the per-env tensors; no synchronisation."""
+        t = self.torch
+        st = self.engine.episode_stats()
+        g = t.zeros(self.num_envs, dtype=t.int64, device=self.engine.device) if groups is None else \
+            t.as_tensor(groups).to(device=self.engine.device, dtype=t.int64)
+        tot = t.zeros((int(n_groups), 8), dtype=t.int64, device=self.engine.device)
+        tot.index_add_(0, g, st["tot"].to(t.int64) & 0xffffffff)
+        ret = t.zeros((int(n_groups), st["sum_ret"].shape[1]), dtype=t.float64, device=self.engine.device)
+        ret.index_add_(0, g, st["sum_ret"])
+        return {"tot": tot, "sum_ret": ret}
 
     @property
     def obs(self):
