@@ -83,7 +83,10 @@ extern "C" {
 #define ZS_RULES_EVACUATION 2
 #define ZS_RULES_SAFEHOUSE 3
 
-/* ---- agent action kinds (int32 triple kind,dx,dy per agent) ------------- */
+/* ---- agent action kinds (int32 triple kind,dx,dy per agent) -------------
+ * dx and dy may be any int32: the target is the agent's cell plus the offset, taken exactly (an offset
+ * beyond the map from any cell of it, +-16 384 or more, names no cell: a move goes nowhere, an attack or
+ * heal finds nothing).  A caller whose offsets are wider than int32 saturates them to the int32 range. */
 #define ZS_ACT_IDLE 0
 #define ZS_ACT_MOVE 1
 #define ZS_ACT_ATTACK 2

@@ -58,6 +58,9 @@ DISCRETE_TRIPLES = np.array([
 ], dtype=np.int32)
 
 
+_I32_MIN, _I32_MAX = -(1 << 31), (1 << 31) - 1
+
+
 class ActionError(Exception):
     """An action the reference's Agent.next_step would raise on."""
 
@@ -69,9 +72,11 @@ def _target_offset(param):
     str -> TypeError)."""
     try:
         ox, oy = 0 + param[0], 0 + param[1]
-        return int(ox), int(oy)
+        ox, oy = int(ox), int(oy)
     except Exception as err:
         raise ActionError(err)
+    # the ABI takes int32 offsets; a Python int beyond them is as far off any map as the range's end
+    return max(_I32_MIN, min(_I32_MAX, ox)), max(_I32_MIN, min(_I32_MAX, oy))
 
 
 def encode_action(action):

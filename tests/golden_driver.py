@@ -133,7 +133,7 @@ def run_config(cfg, K):
     name, surface, stream, kw, seeds, calls, full_calls, max_steps = cfg[:8]
     # extras: poke_obstacles [[i, life], ...] set on the map's Box/Wall objects before the first reset
     # (the reference shares them across resets, game.py:151-155); stream "fixed": `actions`, one dict
-    # action per agent, every step
+    # action per agent, every step; stream "far": `far` = [W, H] of the map, for geometry_shapes.far_action
     extras = cfg[8] if len(cfg) > 8 else {}
     kw = dict(kw)
     kw["map_name"] = K.map_arg(kw["map_name"])
@@ -178,6 +178,10 @@ def run_config(cfg, K):
             else:
                 rec["kind"] = "step"
                 dict_act = A.bad_action if stream == "bad" else A.rich_action
+                if stream == "far":  # geometry_shapes.far_action on a W x H map, offsets up to +-2^40 (Python ints)
+                    import geometry_shapes
+                    W, H = extras["far"]
+                    dict_act = lambda s, t, a: geometry_shapes.far_action(s, t, a, W, H, beyond=True)  # noqa: E731
                 try:
                     if surface == "single":
                         if stream == "discrete":

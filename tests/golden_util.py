@@ -30,10 +30,25 @@ def load_fixture(name):
         return json.load(f)
 
 
+_generated = {}
+
+
 def map_path(name):
-    """A fixture's map: the test-only maps of tests/golden/maps by path, else a bundled map name."""
+    """A fixture's map: the test-only maps of tests/golden/maps by path, a generated map of the geometry table
+    (geometry_shapes.FIXTURE_MAPS) written to a temporary directory, else a bundled map name."""
     p = os.path.join(GOLDEN, "maps", name + ".txt")
-    return p if os.path.isfile(p) else name
+    if os.path.isfile(p):
+        return p
+    import geometry_shapes
+    if name in geometry_shapes.FIXTURE_MAPS:
+        if name not in _generated:
+            import tempfile
+            d = _generated.setdefault("", tempfile.TemporaryDirectory(prefix="zs_geo_"))
+            _generated[name] = os.path.join(d.name, name + ".txt")
+            with open(_generated[name], "w", encoding="utf-8") as f:
+                f.write(geometry_shapes.map_text(geometry_shapes.FIXTURE_MAPS[name]()))
+        return _generated[name]
+    return name
 
 
 def obstacle_pokes(fx):

@@ -86,15 +86,18 @@ def check_death_log(log, prev, cur, A, W, where):
 
 
 def run_engines(builders, make_oracle, seeds, steps, stream_row, graph=False, states_at=(), expect=None,
-                terminal=False):
+                terminal=False, after_step=None):
     """One engine per builder (the same config and seeds under different launch overrides), stepped in lock step
     and each compared with one OracleEnv per env at every step: the reset observation; observations, rewards
     (bit-exact, the listed ones), done, truncated, the autoreset flag and `listed`; the canonical state of every
     env at the steps `states_at`.  expect: per builder, the describe() fields it must report.  terminal: also the
     state of every env at the step it ends or is truncated (the pending env still shows the terminal world) and
     at the step of its autoreset, with ZS_FLAG_DEATH_LOG the death log of the terminal step against the things the
-    oracle removed, and after the last step every env's RNG stream.  Returns per step (1-based; index 0 unused)
-    the number of envs the oracle reset and the number it respawned zombies in."""
+    oracle removed, and after the last step every env's RNG stream.  after_step(t, engs, refs): called after the
+    comparisons of step t (and with t = 0 after the reset).  A stream other than "discrete" goes through step_graph
+    with no policy: the graph replays the step on the guarded action tensor, filled before every call.  Returns
+    per step (1-based; index 0 unused) the number of envs the oracle reset and the number it respawned zombies
+    in."""
     import torch
     from libzombsole_amd.engine import Engine
     from oracle.oracle import OracleEnv
@@ -120,6 +123,8 @@ def run_engines(builders, make_oracle, seeds, steps, stream_row, graph=False, st
         for i in range(len(engs)):
             assert np.array_equal(obs0[i][k], exp), ("reset obs", i, k)
         refs.append(o)
+    if after_step:
+        after_step(0, engs, refs)
     need = [False] * n
     resets, respawns, respawned = [0] * (steps + 1), [0] * (steps + 1), [0] * n
     dlog = terminal and all(e.builder.cfg.flags & 4 for e in engs)  # _abi.FLAG_DEATH_LOG
@@ -129,8 +134,12 @@ def run_engines(builders, make_oracle, seeds, steps, stream_row, graph=False, st
         got = []
         for i, (eng, out) in enumerate(zip(engs, outs)):
             out.clear()
-            if graph:  # the policy's actions are generated inside the replayed graph, into the guarded tensor
+            if graph and stream_row.stream == "discrete":
+                # the policy's actions are generated inside the replayed graph, into the guarded tensor
                 eng.step_graph(t, 7, out=out, actions=out.actions)
+            elif graph:
+                out.actions.copy_(torch.from_numpy(stream_row.actions(seeds, t, A)))
+                eng.step_graph(t, 0, out=out, actions=out.actions)
             else:
                 if stream_row.stream == "discrete":
                     eng.gen_actions(t, 7, out=out.actions)
@@ -175,6 +184,8 @@ def run_engines(builders, make_oracle, seeds, steps, stream_row, graph=False, st
                         check_death_log(eng.death_log(k), before[k], st, A, W, (i, k, t))
             if dlog:
                 before[k] = o.state()
+        if after_step:
+            after_step(t, engs, refs)
         if t in states_at:
             for i, eng in enumerate(engs):
                 for k, o in enumerate(refs):

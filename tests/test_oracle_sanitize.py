@@ -36,6 +36,10 @@ mk = [
 ]
 for m in mk:
     run_hashes(m(1), 5, 6, 40, 7 if m(1).cfg.reward_mode == _abi.REWARD_MULTI else 6, threads=1, reset_twice_mod=2)
+# the far action stream (geometry_shapes.py): offsets up to the ends of int32 on the 257 x 2 strip and the 1 x 16 000 map
+import geometry_shapes
+for rid in ("c257x2", "x1x16000"):
+    assert len(geometry_shapes.oracle_census(geometry_shapes.BY_ID[rid], 3)) == 3
 print("sanitized ok")
 """
 
