@@ -40,9 +40,6 @@ __device__ __forceinline__ int xcd_remap(int b, int nb) {
 // units of it, W consecutive ones per workgroup (one per writer wave).  Measured with
 // tools/probe/storeceil.hip: whole 21 168-B blocks per wave, consecutive waves of an XCD on consecutive
 // blocks ("xcd waveenv") 5.78 TB/s; one block per wave strided over the chip ("chunk 21168") 5.06.
-#ifndef ZS_RING_DEAL
-#define ZS_RING_DEAL 1
-#endif
 struct XcdDeal {
     int base, span, off, w, ucount;
     __device__ XcdDeal(int b, int nb, int n_units, int W) : w(W) {
@@ -82,14 +79,9 @@ __device__ __forceinline__ T obs_val(int v) {
 // int16 blocks (C5) are stored nt (streaming, aux 2): measured on one MI355X (2 runs each), C5's k_obs_ring
 // 196 -> 138.5 us and its tick and reset work 9-10 % shorter (the state they read stays cached); int64
 // blocks keep the default policy (nt: C3 k_obs_ring 227 -> 302 us, the 8 192-env k_obs_pipe 30.7 -> 57.8).
-// -DZS_OBS_AUX=a forces aux a on every dtype (A/B builds).
 template <typename T>
 __device__ __forceinline__ constexpr int obs_aux() {
-#ifdef ZS_OBS_AUX
-    return ZS_OBS_AUX;
-#else
     return sizeof(T) == 2 ? 2 : 0;
-#endif
 }
 template <typename T>
 __device__ __forceinline__ void obs_put(T* p, T v) {
@@ -215,24 +207,25 @@ __device__ __forceinline__ void obs_cell_lds(const Dev& d, const ObsLayout& L, c
 }
 
 // One agent's 21 x 21 channels block into an LDS staging slot (`ot`, elements of S): this lane's
-// cells lane + 64 i.  The lookups of obs_cell_lds are issued level by level for a group of GRP cells
+// cells lane + 64 i.  The lookups of obs_cell_lds are issued level by level for a group of G2 cells
 // (window-map byte, static word and dead-body word of every cell of the group; then their entity pairs
 // and obstacle HP; then the selects and the slot writes), so the LDS round trips of the group overlap.
 // Cell by cell, each cell's slot writes sit between its reads and the next cell's, and (LDS addresses
 // the compiler cannot tell apart) every read waits for them: four dependent LDS waits per cell.
-#ifndef ZS_OBS_GRP
-#define ZS_OBS_GRP 1  // measured on one MI355X (2 runs each): C5 k_obs_lds 241 / 243 us at 1, 286 / 291 at 4
-#endif
-template <typename S, int GRP = ZS_OBS_GRP>
+// Groups of one cell are what ships (measured on one MI355X, 2 runs each: C5 k_obs_lds 241 / 243 us at 1,
+// 286 / 291 at 4).  The group loops stay although they run once: written as a plain per-cell loop the same
+// reads and selects compile to other instructions in k_obs_ring (another schedule, 1-2 VGPRs fewer), a
+// change that needs its own timing.
+template <typename S>
 __device__ __forceinline__ void obs_encode_block(const Dev& d, const ObsLayout& L, const lv4u* st4, const lu8* img,
                                                  const lu8* wm, int ox, int oy, ZS_LDS S* ot, int lane) {
     constexpr int WW = 21, PLANE = WW * WW, PER = (PLANE + 63) / 64;
+    constexpr int G2 = 1;  // cells per group, see above
     const lv2i* ent = (const lv2i*)(img + L.off_life);
     const lu32* dead = (const lu32*)(img + L.off_dead);
     const li32* hpx = (const li32*)(img + L.off_hp);
 #pragma unroll
-    for (int i0 = 0; i0 < PER; i0 += GRP) {
-        constexpr int G2 = GRP;
+    for (int i0 = 0; i0 < PER; i0 += G2) {
         int sb[G2];
         zs_v4u sw[G2];
         uint32_t dw[G2], bit[G2];
@@ -521,23 +514,19 @@ __device__ __forceinline__ zs_v2u obs_dirty(const Dev& d, int e) { return zs_v2u
 __device__ __forceinline__ void obs_prefetch_env(const Dev& d, int e, zs_v2u dirty, ObsPrefetch& f) {
     const int lane = threadIdx.x & 63;
     const int s = lane < d.E ? lane : d.E - 1;
-#ifndef ZS_OBS_DIAG
-#define ZS_OBS_DIAG 0
-#endif
-    const int ee = (ZS_OBS_DIAG & 4) ? 0 : e, ed = (ZS_OBS_DIAG & 2) ? 0 : e, eh = (ZS_OBS_DIAG & 1) ? 0 : e;
-    f.pos = d.pos[EIX(d, s, ee)];
-    f.life = d.life[EIX(d, s, ee)];
-    f.wp = d.weapon[EIX(d, s, ee)];
-    f.pr = d.present[EIX(d, s, ee)];
-    const uint32_t* dr = d.dead + (size_t)ed * d.DW;
+    f.pos = d.pos[EIX(d, s, e)];
+    f.life = d.life[EIX(d, s, e)];
+    f.wp = d.weapon[EIX(d, s, e)];
+    f.pr = d.present[EIX(d, s, e)];
+    const uint32_t* dr = d.dead + (size_t)e * d.DW;
 #pragma unroll
     for (int i = 0; i < OBS_PF_D; i++) {
         const int w = min(lane + 64 * i, d.DW - 1);
         f.dead[i] = (((dirty.y >> ((w * d.dead_chunk_m) >> 20)) & 1u) ? dr : d.dead_zero)[w];
     }
     // an obstacle is cleaned up only at life <= 0, so an env with no HP chunk dirty has every one
-    f.opres = (dirty.x ? d.obst_present + (size_t)ed * d.OW : d.opres_full)[min(lane, max(d.OW - 1, 0))];
-    const int32_t* hr = d.obst_hp + (size_t)eh * d.O;
+    f.opres = (dirty.x ? d.obst_present + (size_t)e * d.OW : d.opres_full)[min(lane, max(d.OW - 1, 0))];
+    const int32_t* hr = d.obst_hp + (size_t)e * d.O;
 #pragma unroll
     for (int i = 0; i < OBS_PF_H; i++) {
         const int o = min(lane + 64 * i, d.O - 1);
@@ -656,14 +645,9 @@ template <> struct obs_stage<int64_t> { typedef int32_t type; };
 
 // (the slot's size: obs_stage_slot_bytes, zs_obs_plan.hpp)
 
-// Stream one staged block to o: slot element k + mis / sizeof(T) holds output element k, so the
-// 16-B chunk q of the destination (counted from the 16-B boundary at or below o) reads the aligned
-// slot elements [q * VPC, (q + 1) * VPC).
-// Buffer-resource stores (raw buffer, gfx9 descriptor word 3): a lane whose offset is past the
-// resource's range is dropped by the hardware, so a masked store needs no branch.  Every flush is then
-// a fixed number of store instructions on every path, and the compiler's vmcnt waits for the next
-// env's prefetch loads (issued before these stores, completing in order) count them exactly instead
-// of assuming the shortest path and draining most of the stores still in flight.
+// Buffer-resource stores (raw buffer, gfx9 descriptor word 3), the flush's head and tail element stores:
+// a lane whose offset is past the resource's range is dropped by the hardware, so a masked store needs
+// no branch.
 #define ZS_OOB 0x80000000u
 
 // base is wave-uniform at every caller (one block per wave); read through readfirstlane so the descriptor
@@ -687,33 +671,21 @@ __device__ __forceinline__ void zs_buf_store(__amdgpu_buffer_rsrc_t r, uint32_t 
     }
 }
 
-// Store throttle: at most ZS_OBS_THR of the wave's memory operations in flight after each 16-B store
-// (-1: none).  HBM write bandwidth on this part falls when the whole chip keeps tens of thousands of
+// Store throttle: at most ZS_OBS_THR of the wave's memory operations in flight after each 16-B store.
+// HBM write bandwidth on this part falls when the whole chip keeps tens of thousands of
 // 1-KB wave stores in flight (tools/probe/storeceil.hip: a flat 16-B store stream reaches 6.6-6.7
 // TB/s with ~2-4 MB in flight chip-wide, 5.0-5.4 TB/s with 2048-4096 waves issuing unthrottled).
 #ifndef ZS_OBS_THR
 #define ZS_OBS_THR 2  // measured on one MI355X, C3 k_obs_lds 343 -> 315 us (4 runs each; vmcnt 1/3/4/6 no better)
 #endif
-#define ZS_STR2(x) #x
-#define ZS_STR(x) ZS_STR2(x)
-__device__ __forceinline__ void obs_store_throttle() {
-#if ZS_OBS_THR >= 0
-    asm volatile("s_waitcnt vmcnt(" ZS_STR(ZS_OBS_THR) ")" ::: "memory");
-#endif
-}
 
 // Stream one staged block to o: slot element k + mis / sizeof(T) holds output element k, so the
 // 16-B chunk q of the destination (counted from the 16-B boundary at or below o) reads the aligned
-// slot elements [q * VPC, (q + 1) * VPC).  The partial chunks at the two ends are element stores.
-// narrow (int16 / int32) blocks: C5's int16 stream moves a quarter of C3's bytes per cell and is not
-// write-bound, so its flush need not hold stores back
-#ifndef ZS_OBS_THR_NARROW
-#define ZS_OBS_THR_NARROW ZS_OBS_THR
-#endif
-#ifndef ZS_FLUSH_GLOBAL
-#define ZS_FLUSH_GLOBAL 1
-#endif
-template <typename T, int NBLK = 1, int THR = (sizeof(T) == 8 ? ZS_OBS_THR : ZS_OBS_THR_NARROW)>
+// slot elements [q * VPC, (q + 1) * VPC).  The whole chunks are plain global stores (on this part a
+// stream of them runs 6 % faster than the same stream of raw buffer stores: tools/probe/storepat2.hip,
+// profiles/r05k_storepat2.log); the partial chunks at the two ends are element stores through the
+// buffer resource.
+template <typename T, int NBLK = 1, int THR = ZS_OBS_THR>
 __device__ __forceinline__ void obs_stage_flush(const lu8* slot, T* o, int lane) {
     typedef typename obs_stage<T>::type S;
     constexpr int TS = (int)sizeof(T), VPC = 16 / TS, NB = NBLK * 3 * 441 * TS;
@@ -733,19 +705,12 @@ __device__ __forceinline__ void obs_stage_flush(const lu8* slot, T* o, int lane)
         } else {
             v = *(const ZS_LDS zs_v4u*)(sv + kr * VPC);
         }
-        if (ZS_FLUSH_GLOBAL) {
-            // plain global stores of the whole 16-B chunks: on this part a stream of them runs 6 % faster than the
-            // same stream of raw buffer stores (tools/probe/storepat2.hip, profiles/r05k_storepat2.log)
-            if (k >= k0 && k < kend) {
-                zs_v4u* dst = (zs_v4u*)((uint8_t*)o - mis) + k;
-                if constexpr (obs_aux<T>() != 0) __builtin_nontemporal_store(v, dst);
-                else *dst = v;
-            }
-        } else {
-            __builtin_amdgcn_raw_buffer_store_b128(v, r, (int)((k >= k0 && k < kend) ? (uint32_t)(16 * k - mis) : ZS_OOB), 0,
-                                                   obs_aux<T>());
+        if (k >= k0 && k < kend) {
+            zs_v4u* dst = (zs_v4u*)((uint8_t*)o - mis) + k;
+            if constexpr (obs_aux<T>() != 0) __builtin_nontemporal_store(v, dst);
+            else *dst = v;
         }
-        if (THR >= 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(THR < 0 ? 0 : THR) : "memory");
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(THR) : "memory");
     }
     const int nhead = mis ? (16 - mis) / TS : 0, tail0 = (16 * kend - mis) / TS, ntail = (nb - 16 * kend) / TS;
     const int idx = lane < nhead ? lane : (lane >= 32 && lane - 32 < ntail) ? tail0 + lane - 32 : -1;
@@ -1030,7 +995,7 @@ struct PatchEnc {
         const int ax = unpack_x(ap), ay = unpack_y(ap);
         const int pbase = ay * PW + ax;  // padded cell of the window's corner (ax - HALF, ay - HALF)
 #pragma unroll
-        for (int i = 0; i < ((ZS_OBS_DIAG & 16) ? 0 : PER); i++) {  // diagnostic builds: 16 skips the encoding
+        for (int i = 0; i < PER; i++) {
             const int cell = lane + 64 * i;
             if (i + 1 < PER || cell < PLANE) {
                 const uint32_t v = pad[pbase + (int)((offp[i / 2] >> (16 * (i % 2))) & 0xffffu)];
@@ -1050,7 +1015,7 @@ struct PatchEnc {
             }
         }
         // dead bodies on cells without a map obstacle (a map obstacle's cell is the list's business)
-        for (int k = lane; k < ((ZS_OBS_DIAG & 32) ? 0 : ndead); k += 64) {  // diagnostic builds: 32 skips them
+        for (int k = lane; k < ndead; k += 64) {
             const uint32_t en = dlist[k];
             const int dx = (int)(en & 0xffffu) - ax + HALF, dy = (int)(en >> 16) - ay + HALF;
             if ((unsigned)dx < (unsigned)WW && (unsigned)dy < (unsigned)WW) {
@@ -1059,7 +1024,7 @@ struct PatchEnc {
                 ot[PLANE + cc] = (S)0;
             }
         }
-        if (ndead < 0 && !(ZS_OBS_DIAG & 32)) {  // more bodies than the list holds: the per-word scan
+        if (ndead < 0) {  // more bodies than the list holds: the per-word scan
             const int c_lo = (ay - HALF) * W, c_hi = (ay + HALF + 1) * W;  // the window's rows
             // maps whose rows are whole words: the window's columns as a mask of each word's bits
             const int x0 = ax - HALF, wpr = W >> 5;
@@ -1124,7 +1089,7 @@ __global__ void __launch_bounds__(64 * PATCH_WPG, ZS_OBS_PIPE_WAVES) k_obs_patch
             T* o = out + ((size_t)e * NOBS + a) * 3 * PLANE;
             pe.block(d, (ZS_LDS S*)slot + (int)((uintptr_t)o & 15) / TS, a);
             wave_sync();
-            if (!(ZS_OBS_DIAG & 8)) obs_stage_flush(slot, o, lane);
+            obs_stage_flush(slot, o, lane);
             wave_sync();
         }
     };
@@ -1176,9 +1141,6 @@ __global__ void __launch_bounds__(64 * PATCH_WPG, ZS_OBS_PIPE_WAVES) k_obs_patch
 #ifndef RING_THR
 #define RING_THR 16
 #endif
-#ifndef ZS_RING_PF
-#define ZS_RING_PF 2  // encoder prefetch depth (items)
-#endif
 
 // The hand-off is LDS-only: a wave's LDS operations complete in order, so waiting for its own LDS
 // traffic (lgkmcnt(0)) before the state store orders the slot's data before the state, and a reader's
@@ -1195,13 +1157,7 @@ __device__ __forceinline__ void ring_wait(const ZS_LDS int* p, int v) {
 }
 
 // PATCHED: the encoders are k_obs_patch's (PatchEnc), static tables patch_static_bytes, encoder regions
-// patch_enc_bytes (ring_patch_lds_bytes)
-__host__ __device__ constexpr int ring_patch_lds_bytes(int static_bytes, int enc_bytes, int tsize, int nobs) {
-    return ring_lds_bytes(static_bytes, enc_bytes, tsize, nobs);
-}
-#ifndef ZS_RING_LAUNDER
-#define ZS_RING_LAUNDER 1
-#endif
+// patch_enc_bytes
 // Dev is the first argument (zs_launder_dev's contract: the encoders reload it from kernarg offset 0)
 template <typename T, int NOBS, bool PATCHED = false>
 __global__ void __launch_bounds__(64 * (RING_ENC + RING_WRT), 1) k_obs_ring(Dev d, T* out, ObsLayout L, int env0, int env1) {
@@ -1229,15 +1185,9 @@ __global__ void __launch_bounds__(64 * (RING_ENC + RING_WRT), 1) k_obs_ring(Dev 
     // unit g covers envs env0 + PAIR * g + h (h < PAIR, below env1); this workgroup's units are
     // g_first, g_first + G, ...; its items (envs) t = PAIR * u + h, the last one possibly absent
     const int G = gridDim.x, n_units = (env1 - env0 + PAIR - 1) / PAIR;
-#if ZS_RING_DEAL
     const XcdDeal deal(blockIdx.x, G, n_units, RING_WRT);
     const int ucount = deal.ucount;
     auto unit_of = [&](int u) { return deal.unit(u); };
-#else
-    const int g_first = xcd_remap(blockIdx.x, G);
-    const int ucount = g_first < n_units ? (n_units - g_first + G - 1) / G : 0;
-    auto unit_of = [&](int u) { return g_first + u * G; };
-#endif
     // items in the last unit: PAIR, or fewer for the run's last unit
     const int count = ucount ? PAIR * (ucount - 1) + min(PAIR, env1 - env0 - PAIR * unit_of(ucount - 1)) : 0;
     auto unit_env = [&](int u) { return env0 + PAIR * unit_of(u); };
@@ -1247,10 +1197,8 @@ __global__ void __launch_bounds__(64 * (RING_ENC + RING_WRT), 1) k_obs_ring(Dev 
             const bool whole = PAIR * u + PAIR <= count;
             for (int h = 0; h < PAIR; h++)
                 if (PAIR * u + h < count) ring_wait(&state[PAIR * q + h], 2 * u + 1);
-            if (!(ZS_OBS_DIAG & 8)) {
-                if (whole) obs_stage_flush<T, NOBS * PAIR, RING_THR>(slots + q * SLOT, out + (size_t)e * BLK, lane);
-                else obs_stage_flush<T, NOBS, RING_THR>(slots + q * SLOT, out + (size_t)e * BLK, lane);
-            }
+            if (whole) obs_stage_flush<T, NOBS * PAIR, RING_THR>(slots + q * SLOT, out + (size_t)e * BLK, lane);
+            else obs_stage_flush<T, NOBS, RING_THR>(slots + q * SLOT, out + (size_t)e * BLK, lane);
             for (int h = 0; h < PAIR; h++) ring_state_store(&state[PAIR * q + h], 2 * u + 2);
         }
         return;
@@ -1263,26 +1211,22 @@ __global__ void __launch_bounds__(64 * (RING_ENC + RING_WRT), 1) k_obs_ring(Dev 
     auto item_env = [&](int t) { return unit_env(t / PAIR) + t % PAIR; };
     int t = wave;
     if (t >= count) return;
-    // encode item t: its image from f, then (before any LDS work) the loads of the item `ahead`
+    // encode item t: its image from f, then (before any LDS work) the loads of the item two
     // iterations later into f, with that item's dirty masks dq (loaded two iterations earlier), and
     // dq reloaded for the item two iterations after that
-    auto encode = [&](int t, ObsPrefetch& f, zs_v2u& dq, int ahead) {
-        // the Dev fields reloaded per item (ZS_RING_LAUNDER), not held in SGPRs across the wave's items
-        const Dev& d = ZS_RING_LAUNDER ? *zs_launder_dev(d0) : d0;
+    auto encode = [&](int t, ObsPrefetch& f, zs_v2u& dq) {
+        // the Dev fields reloaded per item, not held in SGPRs across the wave's items
+        const Dev& d = *zs_launder_dev(d0);
         const int u = t / PAIR, h = t % PAIR, e = item_env(t);
         if (PATCHED) pe.build(d, f);
         else obs_build_compact(d, L, img, f, code_s, lane);
-        // this item's prefetch set next serves item t + ahead * RING_ENC, whose loads need the dirty masks of
-        // the item after that (t + 2 * ahead * RING_ENC)
-        const int tn = t + ahead * RING_ENC, tq = t + 2 * ahead * RING_ENC;
-        if (ahead == 1) {
-            if (tn < count) obs_prefetch(d, item_env(tn), tn + RING_ENC < count ? item_env(tn + RING_ENC) : item_env(tn), f.dirty_ahead, f);
-        } else {
-            // every load unconditional (an item past the wave's last reads the wave's first env again),
-            // so the waits for the older prefetch count the younger one's loads exactly
-            obs_prefetch_env(d, item_env(tn < count ? tn : wave), dq, f);
-            dq = obs_dirty(d, item_env(tq < count ? tq : wave));
-        }
+        // this item's prefetch set next serves item t + 2 * RING_ENC, whose loads need the dirty masks of
+        // the item after that (t + 4 * RING_ENC).  Every load unconditional (an item past the wave's last
+        // reads the wave's first env again), so the waits for the older prefetch count the younger one's
+        // loads exactly
+        const int tn = t + 2 * RING_ENC, tq = t + 4 * RING_ENC;
+        obs_prefetch_env(d, item_env(tn < count ? tn : wave), dq, f);
+        dq = obs_dirty(d, item_env(tq < count ? tq : wave));
         wave_sync();
         if (!PATCHED) obs_window_compact<NOBS>(d, L, img, lane);
         const int q = u % US;
@@ -1290,7 +1234,7 @@ __global__ void __launch_bounds__(64 * (RING_ENC + RING_WRT), 1) k_obs_ring(Dev 
         wave_sync();
         ZS_LDS S* ot0 = (ZS_LDS S*)(slots + q * SLOT) + (int)((uintptr_t)(out + (size_t)(e - h) * BLK) & 15) / TS + h * BLK;
 #pragma unroll
-        for (int a = 0; a < ((ZS_OBS_DIAG & 16) ? 0 : NOBS); a++) {
+        for (int a = 0; a < NOBS; a++) {
             if (PATCHED) {
                 pe.block(d, ot0 + a * 3 * PLANE, a);
             } else {
@@ -1303,7 +1247,6 @@ __global__ void __launch_bounds__(64 * (RING_ENC + RING_WRT), 1) k_obs_ring(Dev 
         ring_state_store(&state[PAIR * q + h], 2 * u + 1);
     };
     auto envc = [&](int tt) { return item_env(tt < count ? tt : wave); };
-#if ZS_RING_PF == 2
     // two items of register prefetch: a load round trip under the saturated store stream outlasts the
     // encoding of one env
     ObsPrefetch fa, fb;
@@ -1313,30 +1256,9 @@ __global__ void __launch_bounds__(64 * (RING_ENC + RING_WRT), 1) k_obs_ring(Dev 
     qa = obs_dirty(d, envc(t + 2 * RING_ENC));
     qb = obs_dirty(d, envc(t + 3 * RING_ENC));
     for (; t < count; t += 2 * RING_ENC) {
-        encode(t, fa, qa, 2);
-        if (t + RING_ENC < count) encode(t + RING_ENC, fb, qb, 2);
+        encode(t, fa, qa);
+        if (t + RING_ENC < count) encode(t + RING_ENC, fb, qb);
     }
-#elif ZS_RING_PF == 3
-    // three items of register prefetch
-    ObsPrefetch fa, fb, fc;
-    zs_v2u qa, qb, qc;
-    obs_prefetch_env(d, envc(t), OBS_OWN_ROWS, fa);
-    obs_prefetch_env(d, envc(t + RING_ENC), obs_dirty(d, envc(t + RING_ENC)), fb);
-    obs_prefetch_env(d, envc(t + 2 * RING_ENC), obs_dirty(d, envc(t + 2 * RING_ENC)), fc);
-    qa = obs_dirty(d, envc(t + 3 * RING_ENC));
-    qb = obs_dirty(d, envc(t + 4 * RING_ENC));
-    qc = obs_dirty(d, envc(t + 5 * RING_ENC));
-    for (; t < count; t += 3 * RING_ENC) {
-        encode(t, fa, qa, 3);
-        if (t + RING_ENC < count) encode(t + RING_ENC, fb, qb, 3);
-        if (t + 2 * RING_ENC < count) encode(t + 2 * RING_ENC, fc, qc, 3);
-    }
-#else
-    ObsPrefetch f;
-    zs_v2u q0 = {0u, 0u};
-    obs_prefetch(d, envc(t), envc(t + RING_ENC), obs_dirty(d, envc(t)), f);
-    for (; t < count; t += RING_ENC) encode(t, f, q0, 1);
-#endif
 }
 
 // ---------------------------------------------------------------------------

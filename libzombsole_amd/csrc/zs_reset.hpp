@@ -97,16 +97,9 @@ __device__ __forceinline__ uint32_t wave_rng_finish(WaveRng& r) {
 // The Dev fields are read through a pointer re-derived from the kernarg segment at each phase (as tick_wg
 // does): read through the kernel's by-value argument they are loaded once and held in SGPRs across the
 // whole rebuild, which spills.  The kernels calling this take their Dev as the first argument.
-#ifndef ZS_RESET_LAUNDER
-#define ZS_RESET_LAUNDER 1
-#endif
-#if ZS_RESET_LAUNDER
 #define ZS_RST_RELOAD() dp = zs_launder_dev(d0)
-#else
-#define ZS_RST_RELOAD() (void)0
-#endif
 __device__ __forceinline__ void reset_env_wave(const Dev& d0, const ResetLds& L, int e, int list_mode, int* err_out) {
-    const Dev* dp = ZS_RESET_LAUNDER ? zs_launder_dev(d0) : &d0;
+    const Dev* dp = zs_launder_dev(d0);
     const int lane = threadIdx.x & 63, N = dp->N, E = dp->E, A = dp->A, P = dp->P;
     RST_DECL
     RST(0);
@@ -355,7 +348,7 @@ __global__ void __launch_bounds__(64, ZS_RESET_WAVES) k_reset(Dev d, int list_mo
 // (core.py:40-66) as wave work (wave_spawn), new zombies appended to the dict order.
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ void respawn_env_wave(const Dev& d0, const ResetLds& L, int e) {
-    const Dev* dp = ZS_RESET_LAUNDER ? zs_launder_dev(d0) : &d0;
+    const Dev* dp = zs_launder_dev(d0);
     const int lane = threadIdx.x & 63, N = dp->N, E = dp->E, Z0 = dp->A + dp->P;
     RST_DECL
     RST(0);

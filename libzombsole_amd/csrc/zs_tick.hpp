@@ -854,9 +854,6 @@ __device__ __forceinline__ zs_v4i grp_read4(const li32* t, const ZS_LDS zs_v4i* 
 // odirty is set when an obstacle was hit.  The lanes
 // exchange their actions through the env's two tables (t0, t1: one word per lane), read back four
 // words at a time.
-#ifndef ZS_DIAG_STOP
-#define ZS_DIAG_STOP 0  // diagnostic builds only (tick_wg): 7-10 end each chunk of grp_execute early
-#endif
 template <int G>
 __device__ __forceinline__ void grp_execute(const Dev& d, Grp& c, int n, int& pos, int& nmoved, int& odirty) {
     const int j = c.j;
@@ -915,7 +912,6 @@ __device__ __forceinline__ void grp_execute(const Dev& d, Grp& c, int n, int& po
         }
         wave_sync();
         GX(3);
-        if (ZS_DIAG_STOP == 7) continue;
         // earlier valid moves of the chunk that leave (vac) or enter (dep) this move's cell.  A lane without a
         // valid move wrote no cell (-1 / -2 match no destination), so the scan compares cells alone, four
         // entries to a nibble, and the earlier-lanes and valid-move conditions apply once, to the masks
@@ -948,7 +944,6 @@ __device__ __forceinline__ void grp_execute(const Dev& d, Grp& c, int n, int& po
             }
         }
         GX(4);
-        if (ZS_DIAG_STOP == 8) continue;
         bool res = !mv || dep == 0ull;
         bool suc = mv && dep == 0ull && !occ0;
         unsigned long long R = gballot<G>(c, res), S = gballot<G>(c, suc);
@@ -978,7 +973,6 @@ __device__ __forceinline__ void grp_execute(const Dev& d, Grp& c, int n, int& po
             }
         }
         GX(5);
-        if (ZS_DIAG_STOP == 9) continue;
         const unsigned long long IR = gballot<G>(c, inr);
         const int r = __popcll(IR & below);
         wave_sync();  // the scans' table reads before the bounds overwrite t1
@@ -987,7 +981,6 @@ __device__ __forceinline__ void grp_execute(const Dev& d, Grp& c, int n, int& po
         grp_draws<G>(d, c, pos, __popcll(IR), [&](int t) { return (int)t1[t]; }, [&](int t, uint32_t v) { t1[t] = (int)v; });
         wave_sync();
         GX(6);
-        if (ZS_DIAG_STOP == 10) continue;
         // every hit on a target in execution order; the last hitter stores the result
         const int hv = inr ? (kind == K_ATTACK ? -(lo + t1[r]) : lo + t1[r]) : 0;
         wave_sync();
@@ -1496,29 +1489,16 @@ __device__ __forceinline__ void bcast_row(lu32* base, int w, uint32_t v) {
 // are loaded in registers right after the first load round and reach LDS only after the decisions, so
 // their round trip (it needs the stream state) overlaps the decisions instead of the stage-in
 // smem: this wave's LDS image (tick_layout)
-#ifndef ZS_TICK_LAUNDER
-#define ZS_TICK_LAUNDER 1
-#endif
-
 template <int G, bool EARLY = false>
 __device__ __forceinline__ void tick_wg(const Dev& d0, int wg, const int32_t* actions, double* rew, uint8_t* done_out,
                                         uint8_t* trunc_out, uint8_t* listed_out, uint8_t* reset_out, int* reset_list,
                                         int* reset_count, void* obs_out, int env0, int env1, lu8* smem) {
-    // The Dev fields are read through a pointer re-derived from the kernarg segment at each phase (ZS_TICK_LAUNDER):
+    // The Dev fields are read through a pointer re-derived from the kernarg segment at each phase:
     // read through the kernel's by-value argument, the compiler loads them all up front and keeps them in SGPRs
     // for the whole tick (458 SGPR spills into VGPR lanes at G = 8, each use a v_readlane).
-    const Dev* dp = ZS_TICK_LAUNDER ? zs_launder_dev(d0) : &d0;
-#if ZS_TICK_LAUNDER
+    const Dev* dp = zs_launder_dev(d0);
 #define ZS_RELOAD_DEV() dp = zs_launder_dev(d0)
-#else
-#define ZS_RELOAD_DEV() (void)0
-#endif
     constexpr int NE = 64 / G;
-#ifndef ZS_DIAG_STOP
-#define ZS_DIAG_STOP 0  // diagnostic builds only: end the tick after phase k (1 stage-in ... 5 MT refill; 6-10 inside the execution; 11-12 in the leader part)
-#endif
-#define ZS_STOP_AFTER(k) \
-    if (ZS_DIAG_STOP == (k)) return
     const int lane = threadIdx.x & 63, g = lane / G, j = lane - g * G;
     const int base = env0 + wg * NE, e = base + g, N = dp->N, E = dp->E, A = dp->A;
     const bool active = e < env1;
@@ -1751,7 +1731,6 @@ __device__ __forceinline__ void tick_wg(const Dev& d0, int wg, const int32_t* ac
     wave_sync();
     STAMP(1);
     ZS_RELOAD_DEV();
-    ZS_STOP_AFTER(1);
     if (stepping) {
         // decisions (start-of-tick state), then the action list of get_actions (core.py:80-101) compacted from
         // them in dict order, when no decision was deferred to the leader (RNG-drawing) or raises:
@@ -1824,7 +1803,6 @@ __device__ __forceinline__ void tick_wg(const Dev& d0, int wg, const int32_t* ac
     wave_sync();
     STAMP(2);
     ZS_RELOAD_DEV();
-    ZS_STOP_AFTER(2);
     if (active && leader && !stepping) {  // this call is the env's reset; outputs as after env.reset()
         int nr = dp->reward_mode == ZS_REWARD_SINGLE ? 1 : A;
         for (int a = 0; a < nr; a++) rew[(size_t)e * nr + a] = 0.0;
@@ -1848,7 +1826,7 @@ __device__ __forceinline__ void tick_wg(const Dev& d0, int wg, const int32_t* ac
         if (nact >= 0 && nact <= 2 * G) {
             int pos = 0, odirty = 0;
             grp_shuffle<G>(*dp, c, nact, pos);
-            if (ZS_DIAG_STOP != 6) grp_execute<G>(*dp, c, nact, pos, nm0, odirty);
+            grp_execute<G>(*dp, c, nact, pos, nm0, odirty);
             if (dp->alog) {  // the executed actions in execution order (drop-in views)
                 int32_t* al = dp->alog + (size_t)e * dp->E * 2;
                 for (int k = j; k < nact; k += G) {
@@ -1867,8 +1845,6 @@ __device__ __forceinline__ void tick_wg(const Dev& d0, int wg, const int32_t* ac
     wave_sync();
     STAMP(3);
     ZS_RELOAD_DEV();
-    ZS_STOP_AFTER(3);
-    if (ZS_DIAG_STOP >= 6 && ZS_DIAG_STOP <= 10) return;  // the execution's own stop points (6: the shuffle only, 7-10 in grp_execute)
     if (leader && stepping) {
         c.n_order = n_order;
         c.t = MISC(c, MISC_T) + 1;
@@ -1887,10 +1863,8 @@ __device__ __forceinline__ void tick_wg(const Dev& d0, int wg, const int32_t* ac
         }
     }
     wave_sync();
-    ZS_STOP_AFTER(11);  // diagnostic builds: 11 after the leader's first part, 12 after the group's cleanup
     env_cleanup_group<G>(*dp, c, stepping);
     wave_sync();
-    ZS_STOP_AFTER(12);
     if (leader && stepping) {
         if (MISC(c, MISC_NMOVED) >= 0) env_step_leader_b(*dp, c, rew, done_out, trunc_out, listed_out);
         if (c.fin && (dp->flags & ZS_FLAG_AUTORESET)) {
@@ -1924,12 +1898,10 @@ __device__ __forceinline__ void tick_wg(const Dev& d0, int wg, const int32_t* ac
     wave_sync();
     STAMP(4);
     ZS_RELOAD_DEV();
-    ZS_STOP_AFTER(4);
     // the MT refill first: its loads do not wait behind the stage-out's stores (one vmcnt for both)
     coop_refill(*dp, base, min(NE, env1 - base), lst, (lu32*)(smem + L.off_bm));
     STAMP(5);
     ZS_RELOAD_DEV();
-    ZS_STOP_AFTER(5);
     if (stepping) {
         for (int s = j; s < E; s += G) {
             dp->pos[EIX(*dp, s, e)] = LP(c, s);
@@ -1964,7 +1936,6 @@ __device__ __forceinline__ void tick_wg(const Dev& d0, int wg, const int32_t* ac
     }
     STAMP(7);
 #undef ZS_RELOAD_DEV
-#undef ZS_STOP_AFTER
 }
 
 // Dev is the first argument: tick_wg reloads it from kernarg offset 0 (zs_launder_dev's contract)
