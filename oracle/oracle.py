@@ -193,7 +193,8 @@ class OracleEnv(object):
 
     def census(self):
         out = np.zeros(len(CENSUS_EXT), dtype=np.int64)
-        self.L.zo_census_ext(self.h, out.ctypes.data, len(out))
+        n = self.L.zo_census_ext(self.h, out.ctypes.data, len(out))
+        assert n == len(CENSUS_EXT), (n, len(CENSUS_EXT))
         return dict(zip(CENSUS_EXT, (int(v) for v in out)))
 
     def poke_obstacle_gone(self, i):
@@ -223,6 +224,23 @@ CENSUS_CASES = CENSUS[:8]
 # ... and the further counters of zo_census_ext / zo_run_hashes_census_ext, which take the buffer's length
 CENSUS_EXT = CENSUS + ("lists_1chunk", "lists_2chunk", "serial_long", "serial_drew", "respawns", "spawn_empty",
                        "spawn_one", "spawn_exact", "spawn_plus1", "spawn_short", "zombies_dropped", "player_fails")
+# ... and the decision census (zs_oracle.h ZO_DC_*): the branches of the reference's next_step functions and of
+# World.thing_attack / thing_heal, counted whether or not the chunk census is on
+CALLERS = ("zombie", "agent_attack", "agent_heal", "terminator", "sniper")  # of closest()
+EDGES = ("claws", "knife", "axe", "gun", "rifle", "shotgun", "heal")
+TARGETS = ("obstacle", "self", "player", "zombie")  # of a randoman's attack / heal
+CENSUS_DECISIONS = (
+    ("z_attack", "z_attack_diag", "z_range_edge_out", "z_move", "z_move_tie", "z_move_offmap",
+     "z_blocked_obst_first", "z_blocked_obst_later") + tuple("z_blocked_skip_dir%d" % k for k in range(4)) +
+    ("z_blocked_tie", "z_blocked_idle") + tuple("z_wander_n%d" % k for k in range(1, 5)) + ("z_wander_stuck",) +
+    tuple("c_tie_" + c for c in CALLERS) + tuple("c_tie_order_" + c for c in CALLERS) +
+    tuple("c_none_" + c for c in CALLERS) + ("hc_self_only",) +
+    ("t_heal_self", "t_attack", "t_move", "t_attack_obstacle", "t_heal_blocker", "t_range_edge_in",
+     "t_range_edge_out", "t_move_tie", "t_best_zombie", "t_best_offmap", "s_attack", "s_idle") +
+    tuple("h_move_n%d" % k for k in range(1, 5)) + ("h_move_offmap", "h_stuck", "r_move", "r_move_offmap") +
+    tuple("r_attack_" + t for t in TARGETS) + tuple("r_heal_" + t for t in TARGETS) +
+    tuple("hit_edge_in_" + w for w in EDGES) + tuple("hit_edge_out_" + w for w in EDGES))
+CENSUS_EXT = CENSUS_EXT + CENSUS_DECISIONS
 
 
 def run_hashes(builder, seed0, n_envs, steps, n_discrete, threads=0, reset_twice_mod=0, chunk_g=0):

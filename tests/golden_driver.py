@@ -133,7 +133,9 @@ def run_config(cfg, K):
     name, surface, stream, kw, seeds, calls, full_calls, max_steps = cfg[:8]
     # extras: poke_obstacles [[i, life], ...] set on the map's Box/Wall objects before the first reset
     # (the reference shares them across resets, game.py:151-155); stream "fixed": `actions`, one dict
-    # action per agent, every step; stream "far": `far` = [W, H] of the map, for geometry_shapes.far_action
+    # action per agent, every step; stream "far": `far` = [W, H] of the map, for geometry_shapes.far_action;
+    # stream "script": `script`, per agent a list of dict actions taken in turn, call c the ((c - 1) % len)-th;
+    # keep_stepping: an env that ended is not reset but stepped on (the reference's envs simply keep stepping)
     extras = cfg[8] if len(cfg) > 8 else {}
     kw = dict(kw)
     kw["map_name"] = K.map_arg(kw["map_name"])
@@ -190,6 +192,9 @@ def run_config(cfg, K):
                         elif stream == "fixed":
                             act = dict(extras["actions"][0])
                             rec["act"] = act
+                        elif stream == "script":
+                            act = dict(extras["script"][0][(call - 1) % len(extras["script"][0])])
+                            rec["act"] = act
                         else:
                             act = dict_act(seed, call, 0)
                             rec["act"] = act
@@ -201,6 +206,9 @@ def run_config(cfg, K):
                                    for i, aid in enumerate(agent_ids)}
                         elif stream == "fixed":
                             act = {aid: dict(extras["actions"][i]) for i, aid in enumerate(agent_ids)}
+                        elif stream == "script":
+                            act = {aid: dict(extras["script"][i][(call - 1) % len(extras["script"][i])])
+                                   for i, aid in enumerate(agent_ids)}
                         else:
                             act = {aid: dict_act(seed, call, i) for i, aid in enumerate(agent_ids)}
                         rec["act"] = [act[a] for a in agent_ids]
@@ -226,7 +234,7 @@ def run_config(cfg, K):
                     trunc = True
                 rec["done"] = bool(done)
                 rec["trunc"] = bool(trunc)
-                if done or trunc:
+                if (done or trunc) and not extras.get("keep_stepping"):
                     need_reset = True
             if surface == "single":
                 ob = obs_bytes_single(obs)

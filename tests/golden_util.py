@@ -60,6 +60,8 @@ def builder_for(fx, num_envs=1, dtype=None):
     kw = dict(fx["kwargs"])
     ms = fx.get("max_steps", 0)
     debug = bool(kw.get("debug", False))
+    # extras "keep_stepping": the env is stepped on after it ended, as the reference's envs let their caller do
+    auto = not (fx.get("extras") or {}).get("keep_stepping")
     if fx["surface"] == "single":
         return _abi.single_env_config(
             num_envs, kw["rules_name"], kw.get("player_names", []), map_path(kw["map_name"]), kw["agent_id"],
@@ -67,14 +69,14 @@ def builder_for(fx, num_envs=1, dtype=None):
             observation_scope=kw.get("observation_scope", "world"),
             observation_position_encoding=kw.get("observation_position_encoding", "simple"),
             agent_weapon=kw.get("agent_weapon", "rifle"), max_episode_steps=ms,
-            obs_dtype=_abi.DTYPE_I32 if dtype is None else dtype, debug=debug)
+            obs_dtype=_abi.DTYPE_I32 if dtype is None else dtype, debug=debug, autoreset=auto)
     return _abi.multi_env_config(
         num_envs, kw["rules_name"], kw.get("player_names", []), map_path(kw["map_name"]), kw["agent_ids"],
         initial_zombies=kw.get("initial_zombies", 0), minimum_zombies=kw.get("minimum_zombies", 0),
         observation_surroundings_width=kw.get("observation_surroundings_width", 21),
         observation_position_encoding_style=kw.get("observation_position_encoding_style", "channels"),
         agent_weapons=kw.get("agent_weapons", "rifle"), max_episode_steps=ms,
-        obs_dtype=_abi.DTYPE_I64 if dtype is None else dtype, debug=debug)
+        obs_dtype=_abi.DTYPE_I64 if dtype is None else dtype, debug=debug, autoreset=auto)
 
 
 def action_triples(fx, rec, n_agents):

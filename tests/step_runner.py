@@ -86,14 +86,15 @@ def check_death_log(log, prev, cur, A, W, where):
 
 
 def run_engines(builders, make_oracle, seeds, steps, stream_row, graph=False, states_at=(), expect=None,
-                terminal=False, after_step=None):
+                terminal=False, after_step=None, keep=False):
     """One engine per builder (the same config and seeds under different launch overrides), stepped in lock step
     and each compared with one OracleEnv per env at every step: the reset observation; observations, rewards
     (bit-exact, the listed ones), done, truncated, the autoreset flag and `listed`; the canonical state of every
     env at the steps `states_at`.  expect: per builder, the describe() fields it must report.  terminal: also the
     state of every env at the step it ends or is truncated (the pending env still shows the terminal world) and
     at the step of its autoreset, with ZS_FLAG_DEATH_LOG the death log of the terminal step against the things the
-    oracle removed, and after the last step every env's RNG stream.  after_step(t, engs, refs): called after the
+    oracle removed, and after the last step every env's RNG stream.  keep: the builders hold no
+    ZS_FLAG_AUTORESET; an env that ended is stepped on, in the engines and in the oracle, and never reset.  after_step(t, engs, refs): called after the
     comparisons of step t (and with t = 0 after the reset).  A stream other than "discrete" goes through step_graph
     with no policy: the graph replays the step on the guarded action tensor, filled before every call.  Returns
     per step (1-based; index 0 unused) the number of envs the oracle reset and the number it respawned zombies
@@ -162,7 +163,7 @@ def run_engines(builders, make_oracle, seeds, steps, stream_row, graph=False, st
                 resets[t] += 1
             else:
                 exp, r, d, tr, lb = o.step(acts[k])
-                need[k] = d or tr
+                need[k] = (d or tr) and not keep
                 c = o.census()["respawns"]
                 respawns[t] += c != respawned[k]
                 respawned[k] = c
