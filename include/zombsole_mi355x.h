@@ -520,7 +520,10 @@ int zs_death_log(zs_handle* h, int32_t env, int32_t* out_host, int32_t cap, int3
 /* The actions env's last zs_step executed, in execution order (World.step's shuffled action list,
  * core.py:76,103-119; replaces reading World.events, core.py:68-70, whose messages the drop-in views
  * derive from it): per action {slot | kind << 8, target} with kind 1 move (target: destination
- * x | y << 16), 2 attack, 3 heal (target: an entity slot, or -1 - obstacle index in map order); at most
+ * x | y << 16, 16 signed bits each: an agent's offset is clamped to +-16384 before it is added, so a destination
+ * off the map stays off the map but a far one is not the cell the caller named; a caller that needs that cell
+ * adds its own offset to the actor's position from before the step, as the drop-in envs do), 2 attack, 3 heal
+ * (target: an entity slot, or -1 - obstacle index in map order); at most
  * cap entries into out_host (2 int32 each); *n_out = how many.  Needs ZS_FLAG_DEATH_LOG; an env reset by
  * that step reports none.  A step a debug raise stopped (ZS_ACT_RAISE) reports *n_out = -1 - k and, as its
  * k entries, the actors before the raising one in dict order that decided an action (core.py:80-101: the

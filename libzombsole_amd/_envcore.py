@@ -21,7 +21,7 @@ import struct
 import numpy as np
 
 from . import _abi
-from .actions import ACT_RAISE, ActionError, encode_action
+from .actions import ACT_MOVE, ACT_RAISE, ActionError, encode_action
 from .engine import Engine, decode_action_log, decode_death_log
 from .game import GameView
 
@@ -154,7 +154,9 @@ class EnvCore(object):
         eng.host_step(self._actions, None if rng == self._rng_last else rng, rec)
         r = self._record(rec)
         random.setstate(r.rng_state())
-        self.game.after_step(pre, r, errors, raising)
+        # the agents' move offsets as given: the action log packs a destination into 16 bits a coordinate
+        moves = {i: (int(t[1]), int(t[2])) for i, t in enumerate(triples) if i not in errors and int(t[0]) == ACT_MOVE}
+        self.game.after_step(pre, r, errors, raising, moves)
         if raising is not None:
             raise errors[raising].args[0]
         return r

@@ -276,13 +276,14 @@ class GameView(object):
             self._views[A + j] = p
         self.world = WorldView(self)
 
-    def after_step(self, pre, rec, errors=None, raising=None):
+    def after_step(self, pre, rec, errors=None, raising=None, moves=None):
         """Book-keeping of a step the env took (EnvCore.tick), from the state record `pre` of the world the
         step started from and the step's host record `rec`: the bodies its cleanup left, in the order it
         removed the things (core.py:121-128), the final values of the removed things into their views (a
         removed zombie's slot may be reused by the same step's respawn), the state after the step, and the
         step's World.events, queued (`errors`: the agents' next_step errors by slot; `raising`: the slot whose
-        error a debug env re-raised)."""
+        error a debug env re-raised; `moves`: the offsets of the agents' move actions by slot, as the caller gave
+        them)."""
         actors = {}
         for slot in pre.order[:pre.n_order]:  # the objects in the world while the step ran
             slot = int(slot)
@@ -300,9 +301,9 @@ class GameView(object):
             self._deco[(x, y)] = ("dead " + v.name) if isinstance(v, Player) else "zombie remains"
         post = StateView(self.engine, rec.state_buf)
         self._cache = post
-        self.world._pending.append((pre, post, actors, deaths, rec.action_log(), errors or {}, raising))
+        self.world._pending.append((pre, post, actors, deaths, rec.action_log(), errors or {}, raising, moves or {}))
 
-    def _step_events(self, pre, post, actors, deaths, alog, errors, raising):
+    def _step_events(self, pre, post, actors, deaths, alog, errors, raising, moves):
         """One step's World.event records (core.py:68-70) in the reference's order: for every actor in dict
         order whose next_step gave no action, 'idle', or 'error with next_step: <err>' when it raised
         (core.py:80-101; a debug env stops at the first error, core.py:96-99); each executed action's result
@@ -310,7 +311,8 @@ class GameView(object):
         core.py:140-202), with positions and occupancy followed through the step's moves; 'died' for every
         thing the cleanup removed, obstacles first in map order, then the others in dict order
         (core.py:121-138).  The actions and their order come from the engine (zs_action_log); the messages
-        are their outcomes against the state from before the step."""
+        are their outcomes against the state from before the step.  `moves`: the agents' move offsets by slot,
+        which give a far destination exactly where the log's 16-bit coordinates cannot."""
         t = pre.t + 1
         W, H = self.world.size
         acts, _ = alog
@@ -341,6 +343,11 @@ class GameView(object):
             if kind == 1:  # thing_move (core.py:140-166)
                 dx, dy = tgt & 0xffff, tgt >> 16
                 dx = dx - 0x10000 if dx >= 0x8000 else dx
+                if slot in moves:
+                    # an agent's destination is its position when the step began plus the offset it gave
+                    # (agent.py:33-37), exactly: the log clamps an offset to +-16384 (zs_action_log), which
+                    # tells on and off the map apart but is not the cell a far move names in its message
+                    dx, dy = int(pre.ent[slot][2]) + moves[slot][0], int(pre.ent[slot][3]) + moves[slot][1]
                 if 0 <= dx < W and 0 <= dy < H:
                     if (dx, dy) in occ:
                         msg = u"hit %s with his head" % occ[(dx, dy)].name

@@ -66,6 +66,10 @@ def load(path):
     L.zo_set_census.argtypes = [C.c_void_p, C.c_int]
     L.zo_census.argtypes = [C.c_void_p, C.c_void_p]
     L.zo_census_ext.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    L.zo_set_logs.restype = None
+    L.zo_set_logs.argtypes = [C.c_void_p, C.c_int]
+    L.zo_action_log.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    L.zo_death_log.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     L.zo_run_hashes_census_ext.restype = C.c_int64
     L.zo_run_hashes_census_ext.argtypes = L.zo_run_hashes_census.argtypes + [C.c_int32]
     return L
@@ -89,6 +93,7 @@ def parse_state(buf):
 
 
 ZO_RAISED = 100
+ALOG_WORDS, DLOG_WORDS = 8, 7  # zs_oracle.h ZO_ALOG_WORDS, ZO_DLOG_WORDS
 
 
 class OracleRaised(Exception):
@@ -136,7 +141,7 @@ class OracleEnv(object):
         rc = self.L.zo_step(self.h, a.ctypes.data, rew.ctypes.data, done.ctypes.data, trunc.ctypes.data,
                             listed.ctypes.data)
         if rc == ZO_RAISED:
-            raise OracleRaised()
+            raise OracleRaised(listed[:self.A].astype(bool))  # args[0]: the agents listed before the step
         if rc:
             raise RuntimeError("zo_step failed: %d" % rc)
         return self.obs(), rew, bool(done[0]), bool(trunc[0]), listed[:self.A].astype(bool)
@@ -199,6 +204,35 @@ class OracleEnv(object):
 
     def poke_obstacle_gone(self, i):
         return self.L.zo_poke_obstacle_gone(self.h, i)
+
+    def set_logs(self, on=True):
+        """Keep every later step's action and death log (zs_oracle.h zo_set_logs; off by default)."""
+        self.L.zo_set_logs(self.h, int(bool(on)))
+
+    def action_log(self):
+        """The last step's actions in execution order, canonical: (n, rows, drew).  A row is ((x, y) of the actor
+        before the step, the actor's thing kind, the action 1 move / 2 attack / 3 heal, the target, took effect)
+        with the target ("cell", x, y) of a move, exact; ("obst", map index); or ("thing", x, y), the target's cell
+        before the step.  n = len(rows), or -1 - len(rows) for a step that raised: the rows are then the decisions
+        before the raising actor in dict order.  drew: a decision drew from the stream."""
+        drew = C.c_int(0)
+        n = self.L.zo_action_log(self.h, None, 0, C.byref(drew))
+        k = -1 - n if n < 0 else n
+        buf = np.zeros((max(k, 1), ALOG_WORDS), dtype=np.int64)
+        self.L.zo_action_log(self.h, buf.ctypes.data, k, None)
+        rows = []
+        for r in buf[:k].tolist():
+            tgt = (("cell", r[5], r[6]), ("obst", r[5]), ("thing", r[5], r[6]))[r[4]]
+            rows.append(((r[0], r[1]), r[2], r[3], tgt, bool(r[7])))
+        return n, rows, bool(drew.value)
+
+    def death_log(self):
+        """The dynamic things the last step's cleanup removed, in removal order: (thing kind, agent / bot index or
+        -1 for a zombie, x, y, life at removal, (x, y) before the step)."""
+        n = self.L.zo_death_log(self.h, None, 0)
+        buf = np.zeros((max(n, 1), DLOG_WORDS), dtype=np.int64)
+        self.L.zo_death_log(self.h, buf.ctypes.data, n)
+        return [(r[0], r[1], r[2], r[3], r[4], (r[5], r[6])) for r in buf[:n].tolist()]
 
 
 def run_batch(builder, seed0, n_envs, steps, n_discrete, threads=1):

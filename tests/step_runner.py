@@ -85,8 +85,60 @@ def check_death_log(log, prev, cur, A, W, where):
     assert new_cells <= cells <= set(cur["dead"]), ("death log cells", where, log, cur["dead"])
 
 
+def engine_action_log(log, pre):
+    """An engine's action log ([(slot, kind, target)], Engine.action_log) in the oracle's canonical form
+    (OracleEnv.action_log without its last field): every thing named by its cell in `pre`, the engine's own state
+    from before the step."""
+    rows = []
+    for slot, kind, tgt in log:
+        r = pre.ent[slot]
+        assert int(r[1]), ("the actor's slot was empty before the step", slot)
+        if kind == 1:
+            x = tgt & 0xffff
+            target = ("cell", x - 0x10000 if x >= 0x8000 else x, tgt >> 16)
+        elif tgt < 0:
+            target = ("obst", -1 - tgt)
+        else:
+            assert int(pre.ent[tgt][1]), ("the target's slot was empty before the step", slot, tgt)
+            target = ("thing", int(pre.ent[tgt][2]), int(pre.ent[tgt][3]))
+        rows.append(((int(r[2]), int(r[3])), int(r[0]), kind, target))
+    return rows
+
+
+def check_logs(eng, k, pre, post, o, zombie_slots, where):
+    """Both logs of env k's last step against the oracle's (OracleEnv.set_logs), entry by entry and in order.
+    Actions: the count (-1 - j after a debug raise), and every entry's actor, kind and target.  Deaths: agent / bot
+    index or zombie, x, y and life at removal; the entry's slot held that thing in the engine's state before the
+    step (its cell there is the oracle's pre-step cell of the thing), the entry's serial is the slot's serial
+    there, and a zombie slot that is taken again after the step carries another serial.  pre, post: the engine's
+    states before and after the step.  Returns whether the step refilled a removed zombie's slot."""
+    A, P = eng.A, eng.builder.num_bots
+    n, rows, _ = o.action_log()
+    acts, raised = eng.action_log(k)
+    got = engine_action_log(acts, pre)
+    assert (-1 - len(got) if raised else len(got)) == n, ("action log count", where, n, acts, raised)
+    assert got == [r[:4] for r in rows], ("action log", where, got, rows)
+    exp = o.death_log()
+    log = eng.death_log(k)
+    assert len(log) == len(exp), ("death log count", where, log, exp)
+    reused = False
+    for (slot, serial, x, y, life), (kind, idx, ex, ey, elife, cell) in zip(log, exp):
+        who = (7, slot) if slot < A else (6, slot - A) if slot < A + P else (5, -1)  # ZS_THING_AGENT, _PLAYER, _ZOMBIE
+        assert (who, x, y, life) == ((kind, idx), ex, ey, elife), ("death log entry", where, log, exp)
+        r = pre.ent[slot]
+        assert int(r[1]) and int(r[0]) == kind and (int(r[2]), int(r[3])) == cell, ("death log slot", where, slot, r, cell)
+        assert int(r[7]) == serial, ("death log serial", where, slot, serial, r)
+        if slot >= A + P and int(post.ent[slot][1]):
+            assert int(post.ent[slot][7]) != serial, ("a refilled slot kept its serial", where, slot, serial)
+            reused = True
+    if any(e[0] == 5 for e in exp) and sum(int(r[1]) for r in post.ent[A + P:]) == zombie_slots:
+        # every zombie slot is taken after the step: each removed zombie's slot was refilled
+        assert all(int(post.ent[e[0]][1]) for e in log if e[0] >= A + P), ("slot reuse", where, log)
+    return reused
+
+
 def run_engines(builders, make_oracle, seeds, steps, stream_row, graph=False, states_at=(), expect=None,
-                terminal=False, after_step=None, keep=False):
+                terminal=False, after_step=None, keep=False, logs=False):
     """One engine per builder (the same config and seeds under different launch overrides), stepped in lock step
     and each compared with one OracleEnv per env at every step: the reset observation; observations, rewards
     (bit-exact, the listed ones), done, truncated, the autoreset flag and `listed`; the canonical state of every
@@ -95,13 +147,16 @@ def run_engines(builders, make_oracle, seeds, steps, stream_row, graph=False, st
     at the step of its autoreset, with ZS_FLAG_DEATH_LOG the death log of the terminal step against the things the
     oracle removed, and after the last step every env's RNG stream.  keep: the builders hold no
     ZS_FLAG_AUTORESET; an env that ended is stepped on, in the engines and in the oracle, and never reset.  after_step(t, engs, refs): called after the
-    comparisons of step t (and with t = 0 after the reset).  A stream other than "discrete" goes through step_graph
+    comparisons of step t (and with t = 0 after the reset).  logs: the builders hold ZS_FLAG_DEATH_LOG; both logs of
+    every env of every engine are compared with the oracle's after every step (check_logs; a reset step reports
+    none), and a step the oracle stops at a debug raise is compared in what it defines: zero rewards, no flag,
+    the state.  A stream other than "discrete" goes through step_graph
     with no policy: the graph replays the step on the guarded action tensor, filled before every call.  Returns
     per step (1-based; index 0 unused) the number of envs the oracle reset and the number it respawned zombies
     in."""
     import torch
     from libzombsole_amd.engine import Engine
-    from oracle.oracle import OracleEnv
+    from oracle.oracle import OracleEnv, OracleRaised
 
     n = len(seeds)
     engs, outs = [], []
@@ -123,9 +178,13 @@ def run_engines(builders, make_oracle, seeds, steps, stream_row, graph=False, st
         exp = o.reset()
         for i in range(len(engs)):
             assert np.array_equal(obs0[i][k], exp), ("reset obs", i, k)
+        if logs:
+            o.set_logs()
         refs.append(o)
     if after_step:
         after_step(0, engs, refs)
+    pre = [[eng.get_state(k) for k in range(n)] for eng in engs] if logs else None
+    zombie_slots = engs[0].E - A - engs[0].builder.num_bots
     need = [False] * n
     resets, respawns, respawned = [0] * (steps + 1), [0] * (steps + 1), [0] * n
     dlog = terminal and all(e.builder.cfg.flags & 4 for e in engs)  # _abi.FLAG_DEATH_LOG
@@ -162,7 +221,11 @@ def run_engines(builders, make_oracle, seeds, steps, stream_row, graph=False, st
                 need[k] = False
                 resets[t] += 1
             else:
-                exp, r, d, tr, lb = o.step(acts[k])
+                try:
+                    exp, r, d, tr, lb = o.step(acts[k])
+                except OracleRaised as err:
+                    assert logs
+                    exp, r, d, tr, lb = None, np.zeros(max(A, 1)), False, False, err.args[0]
                 need[k] = (d or tr) and not keep
                 c = o.census()["respawns"]
                 respawns[t] += c != respawned[k]
@@ -176,7 +239,20 @@ def run_engines(builders, make_oracle, seeds, steps, stream_row, graph=False, st
                 else:
                     assert np.array_equal(g["rewards"][k][lb].view(np.uint64), r[:A][lb].view(np.uint64)), \
                         ("rew", i, k, t, g["rewards"][k], r)
-                assert np.array_equal(g["obs"][k], exp), ("obs", i, k, t)
+                if exp is None:  # a debug raise: of the step's outputs only the state is defined
+                    assert not g["rewards"][k].any(), ("rewards of a raise", i, k, t)
+                    assert engs[i].get_state(k).canonical(kinds) == o.state(), ("state after a raise", i, k, t)
+                else:
+                    assert np.array_equal(g["obs"][k], exp), ("obs", i, k, t)
+            if logs:
+                for i, eng in enumerate(engs):
+                    post = eng.get_state(k)
+                    if r is None:
+                        assert eng.action_log(k) == ([], False) and eng.death_log(k) == [], ("logs of a reset", i, k, t)
+                        assert o.action_log()[0] == 0 and o.death_log() == []
+                    else:
+                        check_logs(eng, k, pre[i][k], post, o, zombie_slots, (i, k, t))
+                    pre[i][k] = post
             if terminal and (need[k] or r is None):
                 st = o.state()
                 for i, eng in enumerate(engs):
