@@ -453,14 +453,15 @@ __device__ __forceinline__ void obs_stream_any(const Dev& d, const ObsLayout& L,
     else obs_stream(d, L, st, img, (int16_t*)out, e);
 }
 
-// k_obs: blockDim/64 envs per workgroup, one env per wave, wave-private LDS images after the
-// workgroup's static tables (stat_words = 4 * DW, or 0).
+// k_obs: blockDim/64 envs per workgroup, one env per wave, wave-private LDS images, then the
+// workgroup's static tables (stat_words = 4 * DW, or 0).  The tables lie after the images: a table at
+// LDS offset 0 is the null pointer of its address space, which obs_stream() takes for "no tables".
 template <typename T>
 __global__ void __launch_bounds__(256) k_obs(Dev d, T* out, const uint8_t* mask, ObsLayout L, int stat_words) {
     if (blockIdx.x == 0 && threadIdx.x == 0) step_tail(d);  // a zs_step's tail (Dev::tail_*)
     extern __shared__ __align__(16) uint8_t smem[];
     const int wave = threadIdx.x >> 6, wpg = blockDim.x >> 6;
-    lu32* st = (lu32*)smem;
+    lu32* st = (lu32*)(smem + wpg * L.bytes);
     if (stat_words) {
         obs_stage_static(d, st, threadIdx.x, blockDim.x);
         __syncthreads();
@@ -468,7 +469,7 @@ __global__ void __launch_bounds__(256) k_obs(Dev d, T* out, const uint8_t* mask,
     const int e = xcd_remap(blockIdx.x, gridDim.x) * wpg + wave;
     if (e >= d.N) return;
     if (mask && !mask[e]) return;
-    lu8* img = (lu8*)(smem + stat_words * 4 + wave * L.bytes);
+    lu8* img = (lu8*)(smem + wave * L.bytes);
     obs_build(d, L, img, e, [&](int s, int& p, int& lf, int& wp, int& pr) {
         p = d.pos[EIX(d, s, e)];
         lf = d.life[EIX(d, s, e)];

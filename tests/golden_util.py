@@ -35,7 +35,8 @@ _generated = {}
 
 def map_path(name):
     """A fixture's map: the test-only maps of tests/golden/maps by path, a generated map of the geometry table
-    (geometry_shapes.FIXTURE_MAPS) written to a temporary directory, else a bundled map name."""
+    (geometry_shapes.FIXTURE_MAPS) or of the observation-shape table (obs_shapes.FIXTURE_MAPS) written to a temporary
+    directory, else a bundled map name."""
     p = os.path.join(GOLDEN, "maps", name + ".txt")
     if os.path.isfile(p):
         return p
@@ -47,6 +48,15 @@ def map_path(name):
             _generated[name] = os.path.join(d.name, name + ".txt")
             with open(_generated[name], "w", encoding="utf-8") as f:
                 f.write(geometry_shapes.map_text(geometry_shapes.FIXTURE_MAPS[name]()))
+        return _generated[name]
+    import obs_shapes
+    if name in obs_shapes.FIXTURE_MAPS:  # the generated fields of the observation-shape table, boxes and objectives too
+        if name not in _generated:
+            import tempfile
+            d = _generated.setdefault("", tempfile.TemporaryDirectory(prefix="zs_geo_"))
+            _generated[name] = os.path.join(d.name, name + ".txt")
+            with open(_generated[name], "w", encoding="utf-8") as f:
+                f.write(obs_shapes.map_text(obs_shapes.FIXTURE_MAPS[name]()))
         return _generated[name]
     return name
 

@@ -13,9 +13,10 @@ static bool lds_never(int, int, int, int, void*) { return false; }
 
 static void print_kernel(const char* name, const ObsKernel& k, int n_envs) {
     printf("\"%s\": {\"kind\": %d, \"name\": \"%s\", \"encoders\": \"%s\", \"nobs\": %d, \"patched\": %d, \"grid\": %u, "
-           "\"block\": %d, \"lds\": %d, \"stat\": %d, \"us\": %d}",
+           "\"block\": %d, \"lds\": %d, \"stat\": %d, \"us\": %d, \"win\": %d, \"hp_cap\": %d, \"img_bytes\": %d, "
+           "\"envs_per_wg\": %d}",
            name, k.kind, obs_kernel_name(k.kind), obs_encoders_name(k), k.nobs, k.patched, obs_grid(k, n_envs), k.block,
-           k.lds, k.stat, k.us);
+           k.lds, k.stat, k.us, k.L.win, k.L.hp_cap, k.L.bytes, k.envs_per_wg);
 }
 
 int main(void) {
@@ -44,7 +45,8 @@ int main(void) {
         print_kernel("full", p.full, s.N);
         printf(", ");
         print_kernel("masked", p.masked, s.N);
-        printf(", \"obs_stat\": %d, \"fobs\": %d, \"step_img_bytes\": %d}\n", p.obs_stat, p.fobs, p.step_img.bytes);
+        printf(", \"obs_stat\": %d, \"fobs\": %d, \"step_img_bytes\": %d, \"step_win\": %d, \"step_hp_cap\": %d}\n", p.obs_stat, p.fobs,
+               p.step_img.bytes, p.step_img.win, p.step_img.hp_cap);
     }
     return 0;
 }
