@@ -134,6 +134,10 @@ extern "C" {
                                    * ends with one more small launch (k_episode_stats).  Without the flag nothing is
                                    * allocated and nothing is launched.  zs_create refuses it on a viewer handle
                                    * (ZS_ESTATE) */
+#define ZS_FLAG_RENDER 64u /* frames of the envs drawn on the device (zs_render*): the handle keeps a body colour per
+                            * cell per env, and every zs_step ends with one more small launch (k_render_track).  Needs
+                            * ZS_FLAG_DEATH_LOG (zs_create: ZS_EINVAL without it); refused on a viewer handle
+                            * (ZS_ESTATE).  Without the flag nothing is allocated and nothing is launched */
 
 /* ---- range flags (zs_overflow) -------------------------------------------
  * The reference's obstacle life is an unbounded Python int that carries over resets
@@ -490,6 +494,44 @@ int zs_episode_stats_get(zs_handle* h, const uint8_t* env_mask_dev, double* run_
                          double* sum_ret_dev, int32_t* last_dev, uint32_t* tot_dev, void* stream);
 int zs_episode_stats_clear(zs_handle* h, const uint8_t* env_mask_dev, void* stream);
 
+/* ---- frames of the envs, drawn on the device (ZS_FLAG_RENDER) ---------------------------------------------
+ * A frame is uint8 [10 H][10 W][3], RGB: the map area (the crop [:10 H, :10 W]) of the image the reference's
+ * OpencvRenderer(W, H + 2 + players).render draws (renderer.py:235-277), pixel for pixel.  The lines below the map
+ * (ticks, life bars, player text) are not drawn.  Cell size 10 and mask size 11 are the reference's.
+ * Per cell, in this order: a present entity draws the disc in its slot's colour (agents blue, zombies green, bots by
+ * type: terminator cyan, sniper yellow, hamster white, randoman red, troll blue); else a present obstacle the wall
+ * (white) or box (yellow), whatever its life; else a body (the env's dead bit) the body mask in the cell's recorded
+ * colour; else an objective the frame (blue).  Every drawn cell paints its 11 x 11 mask at (10 x, 10 y); where the
+ * masks of neighbours share a pixel row or column the cell painted later (x outer, y inner) wins, so pixel (px, py)
+ * takes the first of cell (px / 10, py / 10), the cell above it when py % 10 == 0, the cell left of it when
+ * px % 10 == 0 and the cell above-left when both, whose mask covers it, else black.
+ * A flagged handle keeps body_col, one byte per cell per env (a palette index; rows of W H bytes rounded up to 16):
+ * every zs_step (eager, inside zs_step_graph(_n) for each of its steps, through zs_host_step) ends with one launch
+ * that clears the row of an env the step reset and, for every other env, writes for each entry of the step's death
+ * log the colour of its slot at its cell, in removal order (the last body of a cell gives the colour, as
+ * World.decoration keeps the last).  zs_reset clears the rows of the envs it resets.  zs_set_state leaves the row
+ * alone: a body poked onto a cell without a death this episode has colour 0 and is drawn green.  The flag needs
+ * ZS_FLAG_DEATH_LOG (zs_create: ZS_EINVAL without it, and for a map whose frame would reach 2 GiB) and is refused on
+ * a viewer handle (ZS_ESTATE).  Snapshot records of a flagged handle carry body_col as their last byte section, and
+ * the fingerprint covers the flag.
+ *
+ * zs_render_layout: out[0] = frame height (10 H), out[1] = frame width (10 W), out[2] = frame bytes, out[3] = cell
+ * size (10), out[4] = mask size (11), out[5] = palette entries (8), out[6] = body_col bytes per env, out[7] = byte
+ * offset of the body_col section of the handle's snapshot record.
+ * zs_render: frame k, k < min(n, n_frames), is env envs_dev[k] (NULL: env k), written at out_dev + k * frame bytes;
+ * out_dev is device memory for n_frames frames and needs no alignment.  An entry outside [0, N) is skipped on the
+ * device and its frame keeps its bytes; entries at or past n_frames are not drawn.  Envs may repeat.  One launch on
+ * `stream`, nothing read back, the host not synchronised.  n < 0 or n_frames < 0: ZS_EINVAL; min(n, n_frames) == 0:
+ * nothing.
+ * zs_render_sprites: replaces the atlas: masks[5][4] = the 121-bit masks of solid (wall), box, disc, frame
+ * (objective), body, bit oy * 11 + ox of a mask in word (bit >> 5); palette[8][3] = RGB of entries 0 green (and "no
+ * colour recorded"), 1 blue, 2 cyan, 3 yellow, 4 white, 5 red, 6 and 7 unused.  Waits for the device; later
+ * zs_render calls draw with the new atlas.  The default atlas is the reference's shapes and colours.
+ * All three: ZS_ESTATE on a handle created without ZS_FLAG_RENDER (a viewer handle cannot have it). */
+int zs_render_layout(const zs_handle* h, int32_t out[8]);
+int zs_render(zs_handle* h, const int32_t* envs_dev, int32_t n, uint8_t* out_dev, int32_t n_frames, void* stream);
+int zs_render_sprites(zs_handle* h, const uint32_t masks[5][4], const uint8_t palette[8][3]);
+
 /* Diagnostics (not part of the reference surface): when enabled, every k_tick
  * (the step kernel), k_obs (the observation kernel) and k_reset (world rebuild)
  * launch is bracketed by HIP events on its stream.  zs_profile_read synchronizes
@@ -507,7 +549,8 @@ int zs_profile_read(zs_handle* h, double out[8]);
  * ("patched", "select" or "") the encoders of k_obs_ring; "mask_kernel", "mask_grid", "mask_block" the
  * action-mask launch (zs_action_mask) and "mask_bound" whether a buffer is bound; "env_params" whether the handle
  * carries per-env triples (ZS_FLAG_ENV_PARAMS), "episode_stats" whether it keeps episode statistics
- * (ZS_FLAG_EPISODE_STATS).  Returns ZS_OK. */
+ * (ZS_FLAG_EPISODE_STATS); "render" whether it draws frames (ZS_FLAG_RENDER), "render_grid" k_render's workgroups
+ * per frame and "render_block" their threads (0 without the flag).  Returns ZS_OK. */
 int zs_describe(zs_handle* h, char* buf, int32_t len);
 /* Diagnostics: out[0], out[1] = the two pending-reset list counts, out[2] = the deferred-respawn
  * count (after everything queued on stream), out[3] = the list parity the next step drains. */

@@ -32,6 +32,7 @@ FLAG_DEATH_LOG = 4  # zs_death_log: the drop-in views' decoration order and remo
 FLAG_VIEWER = 8  # a handle that holds other handles' envs for encoding (zs_obs_state_unpack + zs_observe)
 FLAG_ENV_PARAMS = 16  # per-env (initial_zombies, minimum_zombies, max_episode_steps): zs_env_params_set / _get
 FLAG_EPISODE_STATS = 32  # per-env episode statistics kept on the device: zs_episode_stats_*
+FLAG_RENDER = 64  # frames of the envs drawn on the device: zs_render* (the builders set FLAG_DEATH_LOG with it: it needs it)
 OVF_INT16, OVF_INT32 = 1, 2  # zs_overflow range flags
 OVF_PARAM_RANGE = 4  # zs_env_params_set met an entry it did not apply (env or value out of range)
 ENV_PARAMS = ("initial_zombies", "minimum_zombies", "max_episode_steps")  # a per-env triple, in order
@@ -95,12 +96,14 @@ def snapshot_section_bytes(E, O, DW, OW, A):
             E, E, E, A)
 
 
-def snapshot_layout(E, O, DW, OW, A, env_params=False, episode_R=0):
+def snapshot_layout(E, O, DW, OW, A, env_params=False, episode_R=0, body_bytes=0):
     """Mirror of snapshot_layout() (csrc/zs_snapshot.hpp): the byte offset of every section of an env's snapshot
     record, "pad" (where the zero padding starts) and "rec_bytes" (a multiple of 16).  env_params: the record of a
     FLAG_ENV_PARAMS handle, with "env_params" (six int32: the current triple, then the next) before the byte rows.
     episode_R > 0: the record of a FLAG_EPISODE_STATS handle with that many reward slots per env, with "ep_run" (8-byte
-    aligned: run_ret float64 [R], run_flags int32, 4 zero bytes) behind env_params and "ep_bytes"."""
+    aligned: run_ret float64 [R], run_flags int32, 4 zero bytes) behind env_params and "ep_bytes".
+    body_bytes > 0: the record of a FLAG_RENDER handle, with "body_col" (that many bytes: W * H rounded up to 16) behind
+    "listed", the last byte row, and "body_bytes"."""
     L, o = {}, 0
     for name, nbytes in zip(SNAPSHOT_SECTIONS, snapshot_section_bytes(E, O, DW, OW, A)):
         if env_params and name == "weapon":
@@ -112,6 +115,9 @@ def snapshot_layout(E, O, DW, OW, A, env_params=False, episode_R=0):
             o += 8 * episode_R + 8
         L[name] = o
         o += nbytes
+    if body_bytes:
+        L["body_col"], L["body_bytes"] = o, body_bytes
+        o += body_bytes
     L["pad"] = o
     L["rec_bytes"] = (o + 15) // 16 * 16
     return L
@@ -153,6 +159,8 @@ def snapshot_fingerprint(cfg):
         h = _fp_add(h, FLAG_ENV_PARAMS)
     if cfg.flags & FLAG_EPISODE_STATS:
         h = _fp_add(h, FLAG_EPISODE_STATS)
+    if cfg.flags & FLAG_RENDER:
+        h = _fp_add(h, FLAG_RENDER)
     return h
 
 
@@ -258,7 +266,7 @@ class ConfigBuilder(object):
     def __init__(self, num_envs, map_, rules, agent_weapons, agent_codes, bot_types, initial_zombies,
                  minimum_zombies, reward_mode, obs_scope, obs_encoding, obs_width, obs_dtype,
                  max_episode_steps=0, autoreset=True, lanes_per_env=0, debug=False, viewer=False, env_params=False,
-                 episode_stats=False):
+                 episode_stats=False, render=False):
         m = map_ if isinstance(map_, Map) else load_map(map_)
         self.map = m
 
@@ -285,7 +293,8 @@ class ConfigBuilder(object):
                              int(obs_dtype), int(max_episode_steps),
                              (FLAG_AUTORESET if autoreset else 0) | (FLAG_DEBUG if debug else 0) |
                              (FLAG_VIEWER if viewer else 0) | (FLAG_ENV_PARAMS if env_params else 0) |
-                             (FLAG_EPISODE_STATS if episode_stats else 0),
+                             (FLAG_EPISODE_STATS if episode_stats else 0) |
+                             ((FLAG_RENDER | FLAG_DEATH_LOG) if render else 0),
                              int(lanes_per_env))
         self._launch = None
 
@@ -333,7 +342,8 @@ class ConfigBuilder(object):
         E = c.num_agents + c.num_bots + max(c.initial_zombies, c.minimum_zombies)
         L = snapshot_layout(E, m.n_obstacles, (m.width * m.height + 31) // 32, (m.n_obstacles + 31) // 32, c.num_agents,
                             bool(c.flags & FLAG_ENV_PARAMS),
-                            (c.num_agents if c.reward_mode == REWARD_MULTI else 1) if c.flags & FLAG_EPISODE_STATS else 0)
+                            (c.num_agents if c.reward_mode == REWARD_MULTI else 1) if c.flags & FLAG_EPISODE_STATS else 0,
+                            ((m.width * m.height + 15) & ~15) if c.flags & FLAG_RENDER else 0)
         L["fingerprint"] = snapshot_fingerprint(c)
         return L
 
@@ -363,7 +373,7 @@ class ConfigBuilder(object):
 def single_env_config(num_envs, rules_name, player_names, map_name, agent_id, initial_zombies=0,
                       minimum_zombies=0, observation_scope="world", observation_position_encoding="simple",
                       agent_weapon="rifle", max_episode_steps=0, obs_dtype=DTYPE_I32, autoreset=True,
-                      lanes_per_env=0, debug=False, viewer=False, env_params=False, episode_stats=False):
+                      lanes_per_env=0, debug=False, viewer=False, env_params=False, episode_stats=False, render=False):
     """zs_config for the ZombsoleGymEnv surface (gym_env.py:49-83): one agent + bots."""
     m = load_map(map_name)
     rules = rules_id(rules_name)
@@ -373,14 +383,14 @@ def single_env_config(num_envs, rules_name, player_names, map_name, agent_id, in
     enc = parse_encoding(observation_position_encoding)
     return ConfigBuilder(num_envs, m, rules, weapons, [agent_code(agent_id)], bots, initial_zombies,
                          minimum_zombies, REWARD_SINGLE, scope, enc, width, obs_dtype, max_episode_steps,
-                         autoreset, lanes_per_env, debug, viewer, env_params, episode_stats)
+                         autoreset, lanes_per_env, debug, viewer, env_params, episode_stats, render)
 
 
 def multi_env_config(num_envs, rules_name, player_names, map_name, agent_ids, initial_zombies=0,
                      minimum_zombies=0, observation_surroundings_width=21,
                      observation_position_encoding_style="channels", agent_weapons="rifle",
                      max_episode_steps=0, obs_dtype=DTYPE_I64, autoreset=True, lanes_per_env=0, debug=False,
-                     viewer=False, env_params=False, episode_stats=False):
+                     viewer=False, env_params=False, episode_stats=False, render=False):
     """zs_config for the MultiagentZombsoleEnv surface (gym/multiagent_env.py:25-78)."""
     w = int(observation_surroundings_width)
     if (w % 2 == 0) or (w <= 1):
@@ -394,4 +404,4 @@ def multi_env_config(num_envs, rules_name, player_names, map_name, agent_ids, in
     weapons = [weapon_id(n) for n in names]
     return ConfigBuilder(num_envs, m, rules, weapons, [agent_code(a) for a in ids], bots, initial_zombies,
                          minimum_zombies, REWARD_MULTI, OBS_SURROUNDINGS, enc, w, obs_dtype,
-                         max_episode_steps, autoreset, lanes_per_env, debug, viewer, env_params, episode_stats)
+                         max_episode_steps, autoreset, lanes_per_env, debug, viewer, env_params, episode_stats, render)

@@ -9,7 +9,8 @@
 // ABI (seeding, the policy stream, the state views, the drop-ins' per-call records) are k_state.hip's; the per-env
 // record movers (observation-state records, zs_obs_state.hpp; snapshot records, zs_snapshot.hpp and zs_record.hpp) are
 // k_records.hip's; k_env_params.hip scatters per-env zombie counts and time limits (ZS_FLAG_ENV_PARAMS); a
-// ZS_FLAG_EPISODE_STATS handle's step ends with k_episode_stats (k_episode.hip, zs_episode.hpp).
+// ZS_FLAG_EPISODE_STATS handle's step ends with k_episode_stats (k_episode.hip, zs_episode.hpp); a ZS_FLAG_RENDER
+// handle's with k_render_track, and zs_render draws its envs (k_render.hip, zs_render.hpp).
 //
 // Semantics follow the reference exactly (parity: tests/); every sqrt range
 // test of the reference is replaced by its exact integer d^2 equivalent.
@@ -95,6 +96,8 @@ struct zs_handle {
     // [N] byte row the tick writes its reset flags to when the caller passes no reset_dev
     EpisodeArgs ep{};
     uint8_t* d_ep_reset = nullptr;
+    // ZS_FLAG_RENDER: k_render.hip's argument (rn.body_col null without the flag); it shares d_ep_reset
+    RenderArgs rn{};
     // the drop-ins' per-call path (zs_host_*), set up by its first call: one pinned, device-mapped input
     // block (actions, then the `random` state as rings + st words) the kernels read in place, one pinned,
     // device-mapped record block k_host_pack writes in place, one synchronisation per call
@@ -484,6 +487,19 @@ static int create_env_arrays(zs_handle* h, const zs_map_desc& m) {
         TRY(dalloc(h, &a.tot, (size_t)ZS_EP_TOT * N));
         TRY(dalloc(h, &h->d_ep_reset, N));
     }
+    if (d.flags & ZS_FLAG_RENDER) {
+        RenderArgs& a = h->rn;
+        a.N = d.N, a.W = d.W, a.H = d.H, a.E = d.E, a.O = d.O, a.OW = d.OW, a.DW = d.DW;
+        a.plan = render_plan(d.W, d.H);
+        a.pos = d.pos, a.present = d.present, a.scell = d.scell, a.obst_present = d.obst_present, a.dead = d.dead;
+        a.dlog = d.dlog, a.dlog_n = d.dlog_n;
+        a.atlas = render_default_atlas();
+        std::vector<uint8_t> col((size_t)E);
+        for (int s = 0; s < E; s++) col[s] = render_slot_col(s, d.A, d.P, h->cfg.bot_types);
+        TRY(dupload(h, &a.slot_col, col));
+        TRY(dalloc(h, &a.body_col, (size_t)a.plan.body_bytes * N));
+        if (!h->d_ep_reset) TRY(dalloc(h, &h->d_ep_reset, N));
+    }
     return ZS_OK;
 }
 
@@ -540,6 +556,13 @@ extern "C" int zs_create(const zs_config* cfg, int device, zs_handle** out) {
         return fail(ZS_ESTATE, "zs_create: ZS_FLAG_ENV_PARAMS: not on a viewer handle (ZS_FLAG_VIEWER)");
     if ((cfg->flags & ZS_FLAG_EPISODE_STATS) && (cfg->flags & ZS_FLAG_VIEWER))
         return fail(ZS_ESTATE, "zs_create: ZS_FLAG_EPISODE_STATS: not on a viewer handle (ZS_FLAG_VIEWER)");
+    if (cfg->flags & ZS_FLAG_RENDER) {
+        if (cfg->flags & ZS_FLAG_VIEWER) return fail(ZS_ESTATE, "zs_create: ZS_FLAG_RENDER: not on a viewer handle (ZS_FLAG_VIEWER)");
+        if (!(cfg->flags & ZS_FLAG_DEATH_LOG))
+            return fail(ZS_EINVAL, "zs_create: ZS_FLAG_RENDER needs ZS_FLAG_DEATH_LOG (the body colours come from the death log)");
+        if (300L * cfg->map.width * cfg->map.height >= (1L << 31))
+            return fail(ZS_EINVAL, "zs_create: ZS_FLAG_RENDER: a frame of this map would not be below 2 GiB");
+    }
     HIPCHK(hipSetDevice(device));
     HandleOwner owner{new zs_handle()};
     zs_handle* h = owner.h;
@@ -712,6 +735,8 @@ static int queue_reset(zs_handle* h, const uint8_t* env_mask_dev, void* obs_dev,
     }
     // ZS_FLAG_EPISODE_STATS: the reset envs' running return starts over; an abandoned episode is not counted
     if (h->ep.run) HIPCHK(launch_episode_clear(s, h->ep, env_mask_dev, 1));
+    // ZS_FLAG_RENDER: the reset envs' worlds have no bodies
+    if (h->rn.body_col) HIPCHK(launch_render_track(s, h->rn, env_mask_dev, 1));
     return launch_obs(h, h->d, obs_dev, env_mask_dev, s);
 }
 
@@ -744,7 +769,7 @@ extern "C" int zs_step(zs_handle* h, const int32_t* actions_dev, void* obs_dev, 
     HIPCHK(hipSetDevice(h->device));
     // ZS_FLAG_EPISODE_STATS: the update rule reads the tick's reset flags, so a caller that wants none gets the
     // handle's own row (one row whatever the caller's buffers: the step graphs stay keyed on the caller's pointers)
-    if (h->ep.run && !reset_dev) reset_dev = h->d_ep_reset;
+    if ((h->ep.run || h->rn.body_col) && !reset_dev) reset_dev = h->d_ep_reset;
     // 1) rebuild the envs that ended at the previous call (list[p]); fused into the tick launch
     //    when the LDS images allow, else a k_reset launch first
     int q = 1 - h->rpar, rc = ZS_OK;
@@ -826,6 +851,11 @@ extern "C" int zs_step(zs_handle* h, const int32_t* actions_dev, void* obs_dev, 
     if (h->ep.run) {
         const hipError_t ee = launch_episode_stats(s, h->ep, rewards_dev, done_dev, trunc_dev, reset_dev);
         if (ee != hipSuccess) return fail(ZS_EHIP, std::string("k_episode_stats: ") + hipGetErrorString(ee));
+    }
+    // 6) ZS_FLAG_RENDER: the step's death log into the body colours; a reset env's row cleared
+    if (h->rn.body_col) {
+        const hipError_t re = launch_render_track(s, h->rn, reset_dev, 0);
+        if (re != hipSuccess) return fail(ZS_EHIP, std::string("k_render_track: ") + hipGetErrorString(re));
     }
     return ZS_OK;
 }
@@ -1060,7 +1090,8 @@ extern "C" int zs_obs_state_unpack(zs_handle* h, const void* rec_dev, int32_t re
 // ---------------------------------------------------------------------------
 static SnapshotLayout handle_snapshot_layout(const zs_handle* h) {
     const Dev& d = h->d;
-    return snapshot_layout(d.E, d.O, d.DW, d.OW, d.A, (d.flags & ZS_FLAG_ENV_PARAMS) != 0, h->ep.run ? h->ep.R : 0);
+    return snapshot_layout(d.E, d.O, d.DW, d.OW, d.A, (d.flags & ZS_FLAG_ENV_PARAMS) != 0, h->ep.run ? h->ep.R : 0,
+                           h->rn.body_col ? h->rn.plan.body_bytes : 0);
 }
 
 // the engine-side table of a snapshot record (zs_record.hpp): the handle's arrays in record order
@@ -1070,7 +1101,7 @@ static RecTable snapshot_table(const zs_handle* h) {
                                    d.scal, d.hp_dirty, d.dead_dirty, d.rngst, d.prev_life,
                                    d.weapon, d.present, d.order, d.listed};
     return snapshot_rec_table(base, d.E, d.O, d.DW, d.OW, d.A, (size_t)d.N, (d.flags & ZS_FLAG_ENV_PARAMS) ? envp_cur(d) : nullptr,
-                              h->ep.run, h->ep.R);
+                              h->ep.run, h->ep.R, h->rn.body_col, h->rn.plan.body_bytes);
 }
 
 extern "C" int zs_snapshot_layout(const zs_handle* h, int32_t out[24]) {
@@ -1208,6 +1239,55 @@ extern "C" int zs_episode_stats_clear(zs_handle* h, const uint8_t* env_mask_dev,
 }
 
 // ---------------------------------------------------------------------------
+// the envs' picture (ZS_FLAG_RENDER; k_render.hip, zs_render.hpp)
+// ---------------------------------------------------------------------------
+static int render_refused(const zs_handle* h, const char* call) {
+    if (h->rn.body_col) return ZS_OK;
+    return fail(ZS_ESTATE, std::string(call) + ": the handle was created without ZS_FLAG_RENDER");
+}
+
+extern "C" int zs_render_layout(const zs_handle* h, int32_t out[8]) {
+    if (!h || !out) return fail(ZS_EINVAL, "null argument");
+    int rc = render_refused(h, "zs_render_layout");
+    if (rc) return rc;
+    const RenderPlan& p = h->rn.plan;
+    const int32_t v[8] = {p.frame_h, p.frame_w, p.frame_bytes, ZS_RENDER_CELL, ZS_RENDER_MASK, ZS_RENDER_PALETTE, p.body_bytes,
+                          handle_snapshot_layout(h).body_col};
+    std::memcpy(out, v, sizeof(v));
+    return ZS_OK;
+}
+
+extern "C" int zs_render(zs_handle* h, const int32_t* envs_dev, int32_t n, uint8_t* out_dev, int32_t n_frames, void* stream) {
+    if (!h) return fail(ZS_EINVAL, "null handle");
+    int rc = render_refused(h, "zs_render");
+    if (rc) return rc;
+    if (n < 0 || n_frames < 0) return fail(ZS_EINVAL, "zs_render: negative count");
+    const long frames = std::min(n, n_frames);
+    if (frames == 0) return ZS_OK;
+    if (!out_dev) return fail(ZS_EINVAL, "zs_render: null output");
+    if (frames * h->rn.plan.bands > 0x7fffffffL) return fail(ZS_EINVAL, "zs_render: too many frames for one launch");
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(hipSetDevice(h->device));
+    const hipError_t e = launch_render(s, h->rn, envs_dev, n, out_dev, n_frames);
+    if (e != hipSuccess) return fail(ZS_EHIP, std::string("k_render: ") + hipGetErrorString(e));
+    return ZS_OK;
+}
+
+extern "C" int zs_render_sprites(zs_handle* h, const uint32_t masks[5][4], const uint8_t palette[8][3]) {
+    if (!h || !masks || !palette) return fail(ZS_EINVAL, "null argument");
+    int rc = render_refused(h, "zs_render_sprites");
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipDeviceSynchronize());  // the atlas is a launch argument: frames already queued keep the one they took
+    RenderAtlas& a = h->rn.atlas;
+    for (int s = 0; s < RS_NSHAPE - 1; s++)
+        for (int w = 0; w < ZS_RENDER_MASK_WORDS; w++) a.mask[s][w] = masks[s][w] & (w == 3 ? 0x01ffffffu : ~0u);  // 121 bits
+    for (int i = 0; i < ZS_RENDER_PALETTE; i++)
+        a.rgb[i] = (uint32_t)palette[i][0] | ((uint32_t)palette[i][1] << 8) | ((uint32_t)palette[i][2] << 16);
+    return ZS_OK;
+}
+
+// ---------------------------------------------------------------------------
 // An env's MT19937 stream in CPython's random.getstate() form: state[0..623] = the raw
 // block being consumed, state[624] = index of the next word (0..624; 624 = exhausted, the
 // next draw twists).  The single-env wrappers move the process-global `random` state in
@@ -1296,12 +1376,14 @@ extern "C" int zs_describe(zs_handle* h, char* buf, int32_t len) {
              "\"step_wgs_per_cu\": %d, \"rng_window\": %d, \"obs_kernel\": \"%s\", \"reset_side_stream\": %d, "
              "\"reset_lds\": %d, \"respawn\": \"%s\", \"tick_waves\": %d, \"rng_step\": %d, \"par_exec\": %d, "
              "\"obs_kernel_masked\": \"%s\", \"obs_encoders\": \"%s\", \"mask_kernel\": \"k_action_mask\", "
-             "\"mask_grid\": %u, \"mask_block\": %d, \"mask_bound\": %d, \"env_params\": %d, \"episode_stats\": %d}",
+             "\"mask_grid\": %u, \"mask_block\": %d, \"mask_bound\": %d, \"env_params\": %d, \"episode_stats\": %d, "
+             "\"render\": %d, \"render_grid\": %d, \"render_block\": %d}",
              d.N, d.E, p.G, p.fused ? "k_step" : "k_tick", p.lds, p.resident, p.rw_cap,
              d.fobs ? "step launch" : obs_kernel_name(kf.kind), h->reset_side,
              p.reset_lds, p.defer_respawn ? "k_respawn" : "tick", p.tick_waves, p.rw_step,
              d.par_exec, obs_kernel_name(h->obs.masked.kind), obs_encoders_name(kf), zs_mask_grid(d.N), ZS_MASK_BLOCK,
-             h->mask_bound ? 1 : 0, (d.flags & ZS_FLAG_ENV_PARAMS) ? 1 : 0, h->ep.run ? 1 : 0);
+             h->mask_bound ? 1 : 0, (d.flags & ZS_FLAG_ENV_PARAMS) ? 1 : 0, h->ep.run ? 1 : 0, h->rn.body_col ? 1 : 0,
+             h->rn.body_col ? h->rn.plan.bands : 0, h->rn.body_col ? ZS_RENDER_BLOCK : 0);
     return ZS_OK;
 }
 

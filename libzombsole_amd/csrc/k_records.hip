@@ -147,7 +147,7 @@ __global__ __launch_bounds__(256) void k_obs_state_unpack(Dev d, ObsStateLayout 
 // staged in LDS so a lane can index it by section.
 // ---------------------------------------------------------------------------
 static_assert(ZS_SNAP_NSCAL == S_NSCAL && ZS_SNAP_RING == ZS_RING_WORDS, "zs_snapshot.hpp mirrors zs_device.hpp");
-static_assert(SNAP_NSEC + 2 <= REC_MAX_SEC, "a snapshot record's sections (with env_params and ep_run) fit a table");
+static_assert(SNAP_NSEC + 3 <= REC_MAX_SEC, "a snapshot record's sections (with env_params, ep_run and body_col) fit a table");
 static_assert(ZS_SNAP_ENVP == 2 * EP_N, "the env_params section is both triples");
 
 __device__ __forceinline__ void rec_stage_table(const RecTable& arg, RecTable* lds) {

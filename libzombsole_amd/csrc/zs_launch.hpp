@@ -7,6 +7,7 @@
 //   k_mask.hip    k_action_mask (zs_mask.hpp)
 //   k_env_params.hip  k_env_params, k_env_params_get, k_env_params_init, k_env_params_check (ZS_FLAG_ENV_PARAMS)
 //   k_episode.hip  k_episode_stats, k_episode_get, k_episode_clear (ZS_FLAG_EPISODE_STATS; zs_episode.hpp)
+//   k_render.hip  k_render, k_render_track (ZS_FLAG_RENDER; zs_render.hpp)
 //   k_records.hip  the per-env record movers: k_obs_state_pack, k_obs_state_unpack (zs_obs_state.hpp), k_snapshot,
 //                  k_restore, k_pending_list (zs_snapshot.hpp, zs_record.hpp)
 //   k_state.hip   the small helpers: k_seed, k_gen_actions, k_gen_actions_ctr, k_tail, k_get_state, k_set_state,
@@ -16,6 +17,7 @@
 // observation plan's ObsKernel (zs_obs_plan.hpp), plain structs and plain pointers crosses the units.
 #pragma once
 #include "zs_device.hpp"
+#include "zs_render.hpp"  // RenderPlan, RenderAtlas
 
 struct ObsStateLayout;  // zs_obs_state.hpp
 struct RecTable;        // zs_record.hpp
@@ -111,6 +113,29 @@ hipError_t launch_episode_stats(hipStream_t s, const EpisodeArgs& a, const doubl
 hipError_t launch_episode_get(hipStream_t s, const EpisodeArgs& a, const uint8_t* mask, double* run_ret, double* last_ret,
                               double* sum_ret, int32_t* last, uint32_t* tot);
 hipError_t launch_episode_clear(hipStream_t s, const EpisodeArgs& a, const uint8_t* mask, int running);
+
+// the picture of a ZS_FLAG_RENDER handle's envs (k_render.hip; zs_render.hpp).  Like the statistics' arrays, body_col
+// and the atlas are the handle's own and reach these kernels alone, as their argument: the Dev has no field for them.
+struct RenderArgs {
+    int N, W, H, E, O, OW, DW;
+    RenderPlan plan;
+    const int32_t* pos;           // Dev::pos
+    const uint8_t* present;       // Dev::present
+    const int32_t* scell;         // Dev::scell
+    const uint32_t* obst_present; // Dev::obst_present
+    const uint32_t* dead;         // Dev::dead
+    const int32_t* dlog;          // Dev::dlog
+    const int32_t* dlog_n;        // Dev::dlog_n
+    uint8_t* body_col;            // [N][plan.body_bytes]: per cell the palette index of its last body, 0 = none recorded
+    const uint8_t* slot_col;      // [E] static: the palette index of a slot's thing
+    RenderAtlas atlas;
+};
+inline unsigned zs_render_track_grid(int n) { return (unsigned)((n + ZS_RENDER_BLOCK - 1) / ZS_RENDER_BLOCK); }
+// mode 0: a step's tracker (flags: the tick's reset_out, never null); mode 1: clear the rows of the envs whose flag
+// byte is nonzero (null: all).  launch_render: frames k < min(n, n_frames) of env envs[k] (null: k) into
+// out + k * plan.frame_bytes, any alignment; an env outside [0, N) leaves its frame untouched
+hipError_t launch_render_track(hipStream_t s, const RenderArgs& a, const uint8_t* flags, int mode);
+hipError_t launch_render(hipStream_t s, const RenderArgs& a, const int32_t* envs, int n, uint8_t* out, int n_frames);
 
 // per-env records (k_records.hip).  Observation-state records (zs_obs_state.hpp), rec 16-B aligned: the handle's N
 // envs into rec [N][L.rec_bytes]; records [n] into envs env0 .. env0 + n - 1.  Snapshot records (zs_snapshot.hpp) by

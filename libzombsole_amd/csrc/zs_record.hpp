@@ -41,7 +41,7 @@ enum {
     REC_I16 = 1,    // int16 in the record, int32 in the engine: saturated when packed, sign-extended when restored
     REC_BYTE = 2,   // 1 byte in both
 };
-#define REC_MAX_SEC 19  // SNAP_NSEC + 2 (zs_snapshot.hpp): the longest record, a ZS_FLAG_ENV_PARAMS | ZS_FLAG_EPISODE_STATS handle's
+#define REC_MAX_SEC 20  // SNAP_NSEC + 3 (zs_snapshot.hpp): the longest record, a ZS_FLAG_ENV_PARAMS | ZS_FLAG_EPISODE_STATS | ZS_FLAG_RENDER handle's
 
 // Entry nsec of every array stands for the padding (no base, REC_BYTE), so an index that rec_find returns is
 // always inside the arrays.  No section of a table is empty (rec_table leaves empty ones out): the byte after
@@ -233,20 +233,23 @@ ZS_HD inline void rec_copy_chunk(const RecTable& T, RecChunk* row, size_t e, int
 // (current triple, then next), whose record holds them between prev_life and the byte rows, else null; ep_run: the
 // [2 R + 3][N] dword columns of a ZS_FLAG_EPISODE_STATS handle's running part (zs_episode.hpp ZS_EP_RUN_COLS: a zero
 // column, run_ret as dword pairs, run_flags, a zero column), ep_R its R, else null: the record's ep_run section with
-// the alignment gap ahead of it, which the first zero column fills when there is one
+// the alignment gap ahead of it, which the first zero column fills when there is one; body_col: the [N][body_bytes]
+// rows of a ZS_FLAG_RENDER handle, the record's last byte section, else null
 inline RecTable snapshot_rec_table(void* const base[SNAP_NSEC], int E, int O, int DW, int OW, int A, size_t N,
-                                   void* env_params = nullptr, void* ep_run = nullptr, int ep_R = 0) {
+                                   void* env_params = nullptr, void* ep_run = nullptr, int ep_R = 0,
+                                   void* body_col = nullptr, int body_bytes = 0) {
     const size_t rows[SNAP_NSEC] = {ZS_SNAP_RING, (size_t)DW, (size_t)O, (size_t)OW, (size_t)OW, (size_t)E, (size_t)E, (size_t)E,
                                     0, 0, 0, 0, 0, (size_t)E, (size_t)E, (size_t)E, 0};
-    const SnapshotLayout L = snapshot_layout(E, O, DW, OW, A, env_params != nullptr, ep_run ? ep_R : 0);
-    RecSection sec[SNAP_NSEC + 2];
-    int off[SNAP_NSEC + 3], n = 0;
+    const SnapshotLayout L = snapshot_layout(E, O, DW, OW, A, env_params != nullptr, ep_run ? ep_R : 0, body_col ? body_bytes : 0);
+    RecSection sec[SNAP_NSEC + 3];
+    int off[SNAP_NSEC + 4], n = 0;
     for (int s = 0; s < SNAP_NSEC; s++) {
         if (s == SNAP_NWORD && env_params) sec[n] = RecSection{env_params, 0, REC_DWORD}, off[n++] = L.envp;
         if (s == SNAP_NWORD && ep_run)
             sec[n] = RecSection{(uint32_t*)ep_run + (L.ep_gap ? 0 : N), 0, REC_DWORD}, off[n++] = L.ep_run - L.ep_gap;
         sec[n] = RecSection{base[s], rows[s], s < SNAP_NWORD ? REC_DWORD : REC_BYTE}, off[n++] = L.off[s];
     }
+    if (body_col && body_bytes > 0) sec[n] = RecSection{body_col, (size_t)body_bytes, REC_BYTE}, off[n++] = L.body_col;
     off[n] = L.off[SNAP_NSEC];
     return rec_table(sec, off, n, L.rec_bytes, N);
 }

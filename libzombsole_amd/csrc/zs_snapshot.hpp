@@ -35,6 +35,8 @@
 //   the byte rows:
 //     weapon, present, order  u8 [E] each
 //     listed       u8 [A]               ([a][N] columns in the engine)
+//   on a ZS_FLAG_RENDER handle only, the last byte row:
+//     body_col     u8 [W H rounded up to 16]   per cell the palette index of its last body (zs_render.hpp)
 //   zero bytes up to rec_bytes, a multiple of 16.
 // Every 4-byte section is 4-byte aligned in a 16-byte aligned record.
 //
@@ -73,24 +75,29 @@ struct SnapshotLayout {
     int ep_run;              // byte offset of the ep_run section (ZS_FLAG_EPISODE_STATS handles), 8-byte aligned, else 0
     int ep_bytes;            // its bytes, 8 R + 8, else 0
     int ep_gap;              // zero bytes ahead of it (0 or 4)
+    int body_col;            // byte offset of the body_col section (ZS_FLAG_RENDER handles), else 0
+    int body_bytes;          // its bytes, else 0
 };
 
 // env_params: the record of a ZS_FLAG_ENV_PARAMS handle, which holds one section more, env_params i32 [ZS_SNAP_ENVP]
 // (the engine's [6][N] columns), after prev_life, the last of the 4-byte sections, and before the byte rows
 // ep_R: the record of a ZS_FLAG_EPISODE_STATS handle with R reward slots per env (0: none), which holds ep_run behind
 // env_params (if any) and before the byte rows
-ZS_HD inline SnapshotLayout snapshot_layout(int E, int O, int DW, int OW, int A, bool env_params = false, int ep_R = 0) {
+// body_bytes: the record of a ZS_FLAG_RENDER handle (0: none), which holds body_col behind listed, the last byte row
+ZS_HD inline SnapshotLayout snapshot_layout(int E, int O, int DW, int OW, int A, bool env_params = false, int ep_R = 0,
+                                            int body_bytes = 0) {
     const int bytes[SNAP_NSEC] = {4 * ZS_SNAP_RING, 4 * DW, 4 * O, 4 * OW, 4 * OW, 4 * E, 4 * E, 4 * E,
                                   4 * ZS_SNAP_NSCAL, 4, 4, 4, 4 * A,
                                   E, E, E, A};
     SnapshotLayout L;
-    L.envp = L.ep_run = L.ep_bytes = L.ep_gap = 0;
+    L.envp = L.ep_run = L.ep_bytes = L.ep_gap = L.body_col = L.body_bytes = 0;
     int o = 0;
     for (int s = 0; s < SNAP_NSEC; s++) {
         if (s == SNAP_NWORD && env_params) L.envp = o, o += 4 * ZS_SNAP_ENVP;
         if (s == SNAP_NWORD && ep_R > 0) L.ep_gap = o & 4, L.ep_run = o + L.ep_gap, L.ep_bytes = 8 * ep_R + 8, o = L.ep_run + L.ep_bytes;
         L.off[s] = o, o += bytes[s];
     }
+    if (body_bytes > 0) L.body_col = o, L.body_bytes = body_bytes, o += body_bytes;
     L.off[SNAP_NSEC] = o;
     L.rec_bytes = (o + 15) & ~15;
     return L;
@@ -102,8 +109,8 @@ ZS_HD inline SnapshotLayout snapshot_layout(int E, int O, int DW, int OW, int A,
 // zombies, and the static tables: obstacle cells and kinds, player and zombie spawn lists, objective cells, agent
 // weapons, bot types (each with its length).  Deliberately not covered: the env count, the observation settings
 // (scope, encoding, width, dtype, agent codes), lanes_per_env, the launch overrides and the flags, but for
-// ZS_FLAG_ENV_PARAMS and ZS_FLAG_EPISODE_STATS: a handle with either has a longer record, so the flag is hashed in
-// (last, in that order, and only when set: the fingerprints of handles without them are what they were).
+// ZS_FLAG_ENV_PARAMS, ZS_FLAG_EPISODE_STATS and ZS_FLAG_RENDER: a handle with any of them has a longer record, so the
+// flag is hashed in (last, in that order, and only when set: the fingerprints of handles without them are what they were).
 // ---------------------------------------------------------------------------
 inline uint64_t snapshot_fp_add(uint64_t h, uint64_t v) {  // splitmix64's finaliser over the running value
     uint64_t z = (h ^ v) + 0x9E3779B97F4A7C15ull;
@@ -136,5 +143,6 @@ inline uint64_t snapshot_fingerprint(const zs_config* c) {
     h = snapshot_fp_table(h, c->bot_types, c->num_bots);
     if (c->flags & ZS_FLAG_ENV_PARAMS) h = snapshot_fp_add(h, (uint64_t)ZS_FLAG_ENV_PARAMS);
     if (c->flags & ZS_FLAG_EPISODE_STATS) h = snapshot_fp_add(h, (uint64_t)ZS_FLAG_EPISODE_STATS);
+    if (c->flags & ZS_FLAG_RENDER) h = snapshot_fp_add(h, (uint64_t)ZS_FLAG_RENDER);
     return h;
 }

@@ -20,7 +20,8 @@ SYMBOLS = ["zs_last_error", "zs_create", "zs_destroy", "zs_obs_shape", "zs_seed"
            "zs_snapshot_layout", "zs_snapshot", "zs_restore",
            "zs_action_mask", "zs_action_mask_bind",
            "zs_env_params_set", "zs_env_params_get", "zs_env_params_check",
-           "zs_episode_stats_layout", "zs_episode_stats_get", "zs_episode_stats_clear"]
+           "zs_episode_stats_layout", "zs_episode_stats_get", "zs_episode_stats_clear",
+           "zs_render_layout", "zs_render", "zs_render_sprites"]
 
 _lib = None
 
@@ -89,6 +90,9 @@ def load_library(path=None):
     L.zs_episode_stats_layout.argtypes = [vp, C.POINTER(i32)]
     L.zs_episode_stats_get.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
     L.zs_episode_stats_clear.argtypes = [vp, vp, vp]
+    L.zs_render_layout.argtypes = [vp, C.POINTER(i32)]
+    L.zs_render.argtypes = [vp, vp, i32, vp, i32, vp]
+    L.zs_render_sprites.argtypes = [vp, vp, vp]
     for s in SYMBOLS:
         if s != "zs_last_error":
             getattr(L, s).restype = C.c_int
@@ -523,6 +527,53 @@ class Engine(object):
         rc = self.L.zs_episode_stats_clear(self.h, _ptr(mask), self._stream())
         if rc:
             _raise(self.L, rc, "zs_episode_stats_clear")
+
+    # -- frames of the envs (zs_render*; a config with FLAG_RENDER) ------------------------------------------------
+    def render_layout(self):
+        """zs_render_layout as a dict: "height", "width", "frame_bytes", "cell", "mask", "palette", "body_bytes" (the
+        body colours' bytes per env) and "body_col" (their offset in the handle's snapshot record)."""
+        if getattr(self, "_rnl", None) is None:
+            out = (C.c_int32 * 8)()
+            rc = self.L.zs_render_layout(self.h, out)
+            if rc:
+                _raise(self.L, rc, "zs_render_layout")
+            self._rnl = dict(zip(("height", "width", "frame_bytes", "cell", "mask", "palette", "body_bytes", "body_col"),
+                                 [int(v) for v in out]))
+        return self._rnl
+
+    def render(self, envs=None, out=None):
+        """Frames of the envs as a uint8 [n, 10 H, 10 W, 3] RGB device tensor (zs_render: one launch, no
+        synchronisation), pixel-exact to the map area of the reference's OpencvRenderer.  `envs`: an int32 device
+        tensor (or a sequence) of env indices, repeats allowed, default every env in order; an index outside [0, N)
+        leaves its frame as it is (zero in a tensor this call allocates).  `out`: a contiguous uint8 device tensor
+        [m, 10 H, 10 W, 3] to draw into; with m < n only the first m entries are drawn.  Without `out` the frames are
+        allocated zero-filled on every call (1.2 MB per bridge64 frame: a memset of the whole tensor ahead of the
+        draw), so a caller that draws many envs or draws every step passes its own `out`."""
+        t = self.torch
+        L = self.render_layout()
+        if envs is not None and not t.is_tensor(envs):
+            envs = t.as_tensor(np.asarray(envs, dtype=np.int32).reshape(-1), device=self.device)
+        if envs is not None and (envs.dtype != t.int32 or envs.dim() != 1 or not envs.is_contiguous() or envs.device != self.device):
+            raise ValueError("render: envs is a contiguous int32 tensor [n] on %s" % (self.device,))
+        n = self.N if envs is None else int(envs.numel())
+        if out is None:
+            out = t.zeros((n, L["height"], L["width"], 3), dtype=t.uint8, device=self.device)
+        if (out.dtype != t.uint8 or out.dim() != 4 or tuple(out.shape[1:]) != (L["height"], L["width"], 3) or
+                not out.is_contiguous() or out.device != self.device):
+            raise ValueError("render: out is a contiguous uint8 tensor [m, %d, %d, 3] on %s" % (L["height"], L["width"], self.device))
+        rc = self.L.zs_render(self.h, _ptr(envs), n, _ptr(out), int(out.shape[0]), self._stream())
+        if rc:
+            _raise(self.L, rc, "zs_render")
+        return out
+
+    def set_render_atlas(self, masks, palette):
+        """Replace the sprite atlas (zs_render_sprites; waits for the device): `masks` uint32 [5, 4], the 121-bit masks
+        of render.SHAPES, `palette` uint8 [8, 3] RGB (render.default_atlas() gives the reference's)."""
+        m = np.ascontiguousarray(np.asarray(masks, dtype=np.uint32).reshape(5, 4))
+        pal = np.ascontiguousarray(np.asarray(palette, dtype=np.uint8).reshape(8, 3))
+        rc = self.L.zs_render_sprites(self.h, _np_ptr(m), _np_ptr(pal))
+        if rc:
+            _raise(self.L, rc, "zs_render_sprites")
 
     def gen_actions(self, step, n_discrete, out=None):
         o = self.actions if out is None else out

@@ -67,19 +67,19 @@ class BatchedZombsole(object):
                  observation_scope="world", observation_position_encoding="simple", agent_weapon="rifle",
                  observation_surroundings_width=21, observation_position_encoding_style="channels",
                  agent_weapons="rifle", obs_dtype=None, autoreset=True, device=None, lanes_per_env=0,
-                 action_masks=False, env_params=False, episode_stats=False):
+                 action_masks=False, env_params=False, episode_stats=False, render=False):
         if surface == "single":
             b = _abi.single_env_config(num_envs, rules_name, player_names, map_name, agent_id, initial_zombies,
                                        minimum_zombies, observation_scope, observation_position_encoding,
                                        agent_weapon, max_episode_steps,
                                        _abi.DTYPE_I32 if obs_dtype is None else obs_dtype, autoreset, lanes_per_env,
-                                       env_params=env_params, episode_stats=episode_stats)
+                                       env_params=env_params, episode_stats=episode_stats, render=render)
         elif surface == "multi":
             b = _abi.multi_env_config(num_envs, rules_name, player_names, map_name, agent_ids, initial_zombies,
                                       minimum_zombies, observation_surroundings_width,
                                       observation_position_encoding_style, agent_weapons, max_episode_steps,
                                       _abi.DTYPE_I64 if obs_dtype is None else obs_dtype, autoreset, lanes_per_env,
-                                      env_params=env_params, episode_stats=episode_stats)
+                                      env_params=env_params, episode_stats=episode_stats, render=render)
         else:
             raise ValueError("surface must be 'single' or 'multi'")
         self.surface = surface
@@ -144,6 +144,12 @@ class BatchedZombsole(object):
         ret = t.zeros((int(n_groups), st["sum_ret"].shape[1]), dtype=t.float64, device=self.engine.device)
         ret.index_add_(0, g, st["sum_ret"])
         return {"tot": tot, "sum_ret": ret}
+
+    # -- frames (render=True): the envs' picture, drawn on the device ------------------------------------------------
+    def render(self, envs=None, out=None):
+        """Engine.render: uint8 [n, 10 H, 10 W, 3] RGB frames of `envs` (default: all) on the device, pixel-exact to
+        the map area of the reference's OpencvRenderer; no synchronisation."""
+        return self.engine.render(envs, out)
 
     @property
     def obs(self):
