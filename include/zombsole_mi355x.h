@@ -249,7 +249,7 @@ int zs_seed(zs_handle* h, int32_t env0, int32_t n, const uint64_t* seeds_host, v
 /* Reset the envs whose byte in env_mask_dev is nonzero (NULL = all) and write
  * their reset observations into obs_dev (other envs' slices untouched).  A new
  * handle's envs are all pending reset: the first zs_step resets them if zs_reset
- * was not called. */
+ * was not called.  obs_dev may be NULL: the envs are reset and no grid observation is written. */
 int zs_reset(zs_handle* h, const uint8_t* env_mask_dev, void* obs_dev, void* stream);
 
 /* Re-encode the observation of the envs whose mask byte is nonzero (NULL = all)
@@ -265,7 +265,10 @@ int zs_observe(zs_handle* h, const uint8_t* env_mask_dev, void* obs_dev, void* s
  *   listed_dev       uint8 [N][num_agents]: agent was in env.agents before the
  *                    step (multi surface: the keys of the returned dicts)
  *   reset_dev        uint8 [N]: 1 when this call reset the env (autoreset)
- * Any output pointer except obs/rewards/done/trunc may be NULL.
+ * Any output pointer except rewards/done/trunc may be NULL.  With obs_dev NULL no grid observation is written, by
+ * the step launch, the reset work or an observation launch, and the step's last launch of its own is the tail
+ * (k_tail); everything else the step computes is what it computes with a buffer.  The same holds for every step of
+ * zs_step_graph(_n).  A learner on entity observations (zs_entity_obs_bind) steps this way.
  * zs_step does not report a reset that fails for want of player spawn cells (the implicit first reset, an
  * autoreset): it returns ZS_OK, reports the env as reset, and leaves it as the failing
  * Game.__initialize_world__ left it (the players that fit placed, no zombies, the stream after the draws made).
@@ -428,6 +431,40 @@ int zs_restore(zs_handle* h, const void* rec_dev, int32_t rec_bytes, int32_t n_r
 int zs_action_mask(zs_handle* h, const uint8_t* env_mask_dev, void* mask_dev, void* stream);
 int zs_action_mask_bind(zs_handle* h, void* mask_dev_or_null);
 
+/* ---- entity observations: a few hundred bytes per env instead of the grid ---------------------------------
+ * out_dev is int16 [N][num_agents][ROW], ROW = 16 + 4 (kz + kp) words, 8-byte aligned (else ZS_EINVAL), with
+ * 1 <= kz <= 16 zombie rows and 0 <= kp <= 16 player rows (else ZS_EINVAL, before any launch).  Every value is an
+ * exact integer of the env's current world, the one its grid observation shows (an env pending its reset: the
+ * terminal world).  A row, in words (E slots: agents [0,A), bots [A,A+P), zombies [A+P,E)):
+ *   self       8  present (1), x, y, life, weapon code (ZS_WEAPON_*), weapon_r2 (the largest integer d2 inside the
+ *                 weapon's range: 2, 36, 100, 9), zombies present in the env, other agents and bots present
+ *   zombies    kz x {dx, dy, life, flags}: the present zombie slots ascending by (d2, slot), d2 = dx^2 + dy^2 and
+ *                 dx, dy the zombie's cell minus the agent's; flags bit 0 valid, bit 1 d2 <= weapon_r2, bit 2
+ *                 d2 == 1; rows past the present zombies are zero
+ *   players    kp x {dx, dy, life, flags}: the present agent and bot slots other than the agent itself, in the
+ *                 same order; flags bit 0 valid, bit 1 d2 <= 9 (HEALING_RANGE), bit 2 an agent and not a bot,
+ *                 bits 8..15 its weapon code
+ *   objective  4  {dx, dy, flags, n_objectives} of the nearest objective cell by (d2, map-file index); flags bit 0
+ *                 valid, bit 1 the agent stands on an objective
+ *   rays       4  towards (0,1), (-1,0), (0,-1), (1,0): the consecutive cells, starting next to the agent, that
+ *                 are inside the map and hold no present obstacle (whatever its life), at most 16; entities do not
+ *                 stop a ray
+ * Lives and counts saturate to the int16 range.  An agent that is not in the world has an all-zero row.
+ * The tie-break among equidistant slots is the slot number, not the reference's dict order: among equidistant
+ * zombies row 0 need not be the one attack_closest hits (bit 1 of row 0 still equals action-mask byte 4).
+ *
+ * zs_entity_obs_layout: out[0] = ROW in words, out[1..5] = the word offsets of self, zombies, players, objective and
+ * rays, out[6] = the ray cap (16), out[7] = the row's bytes.
+ * zs_entity_obs: one launch on `stream` for the envs whose env_mask_dev byte is nonzero (NULL = all); other envs'
+ * bytes are untouched.  Any handle: a viewer's envs (zs_obs_state_unpack) hold everything the kernel reads.
+ * zs_entity_obs_bind: while a buffer is bound (non-NULL), every zs_step ends with a launch of all envs into it, after
+ * the observation / tail launch and a bound mask launch, eagerly, for each step of zs_step_graph(_n) and through
+ * zs_host_step.  Binding another buffer, other K values or NULL drops the cached graphs.  A handle that never binds
+ * launches what it did before.  The buffer must outlive the binding.  ZS_ESTATE on a viewer handle. */
+int zs_entity_obs_layout(const zs_handle* h, int32_t kz, int32_t kp, int32_t out[8]);
+int zs_entity_obs(zs_handle* h, const uint8_t* env_mask_dev, int32_t kz, int32_t kp, void* out_dev, void* stream);
+int zs_entity_obs_bind(zs_handle* h, void* out_dev_or_null, int32_t kz, int32_t kp);
+
 /* ---- per-env zombie counts and time limits (ZS_FLAG_ENV_PARAMS) ----------------------------------------
  * A flagged handle holds, per env, the triple (initial_zombies, minimum_zombies, max_episode_steps) twice: the
  * NEXT triple and the CURRENT one.  After zs_create both equal the config's values, and until the first
@@ -550,7 +587,11 @@ int zs_profile_read(zs_handle* h, double out[8]);
  * action-mask launch (zs_action_mask) and "mask_bound" whether a buffer is bound; "env_params" whether the handle
  * carries per-env triples (ZS_FLAG_ENV_PARAMS), "episode_stats" whether it keeps episode statistics
  * (ZS_FLAG_EPISODE_STATS); "render" whether it draws frames (ZS_FLAG_RENDER), "render_grid" k_render's workgroups
- * per frame and "render_block" their threads (0 without the flag).  Returns ZS_OK. */
+ * per frame and "render_block" their threads (0 without the flag); "entity_obs_bound" whether an entity-observation
+ * buffer is bound (zs_entity_obs_bind) and "entity_kz", "entity_kp" its K values (0 when none);
+ * "step_tail_launch" the launch that carried the tail of the last zs_step queued or captured: the observation kernel,
+ * or "k_tail" when the step launch wrote the observations itself or obs_dev was NULL ("" before any step).
+ * Returns ZS_OK. */
 int zs_describe(zs_handle* h, char* buf, int32_t len);
 /* Diagnostics: out[0], out[1] = the two pending-reset list counts, out[2] = the deferred-respawn
  * count (after everything queued on stream), out[3] = the list parity the next step drains. */

@@ -126,6 +126,21 @@ def snapshot_layout(E, O, DW, OW, A, env_params=False, episode_R=0, body_bytes=0
 _M64 = (1 << 64) - 1
 
 
+ENTITY_LAYOUT_KEYS = ("row_words", "self", "zombies", "players", "objective", "rays", "ray_cap", "row_bytes")
+ENTITY_KMAX, ENTITY_RAY_CAP = 16, 16
+
+
+def entity_layout(kz, kp):
+    """zs_entity_obs_layout on the host: the int16 row of an entity observation with kz zombie rows (1..16) and kp
+    player rows (0..16), as a dict of ENTITY_LAYOUT_KEYS (word offsets; "row_bytes" = 2 * "row_words")."""
+    kz, kp = int(kz), int(kp)
+    if not (1 <= kz <= ENTITY_KMAX and 0 <= kp <= ENTITY_KMAX):
+        raise ValueError("entity observation: kz must be in 1..16 and kp in 0..16")
+    words = 16 + 4 * (kz + kp)
+    return dict(zip(ENTITY_LAYOUT_KEYS, (words, 0, 8, 8 + 4 * kz, 8 + 4 * (kz + kp), 12 + 4 * (kz + kp), ENTITY_RAY_CAP,
+                                         2 * words)))
+
+
 def _fp_add(h, v):
     z = ((h ^ (v & _M64)) + 0x9E3779B97F4A7C15) & _M64
     z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64

@@ -5,7 +5,8 @@
 // fused with it into k_step), k_tick (zs_tick.hpp, 64/G envs per wave with G lanes per env and the env's hot state
 // in LDS), k_respawn (deferred zombie respawns, one wave per env) and the observation kernel (zs_obs.hpp: k_obs_ring /
 // k_obs_pipe persistent store streams, k_obs_gather for large maps, k_obs in general), else k_tail, then k_action_mask
-// (zs_mask.hpp) when a mask buffer is bound.  zs_step_graph replays a step as a hipGraph.  The small helpers behind the
+// (zs_mask.hpp) when a mask buffer is bound and k_entity_obs (k_entity_obs.hip, zs_entity_obs.hpp) when an entity
+// buffer is.  With a null obs_dev no grid observation is written and k_tail ends the step.  zs_step_graph replays a step as a hipGraph.  The small helpers behind the
 // ABI (seeding, the policy stream, the state views, the drop-ins' per-call records) are k_state.hip's; the per-env
 // record movers (observation-state records, zs_obs_state.hpp; snapshot records, zs_snapshot.hpp and zs_record.hpp) are
 // k_records.hip's; k_env_params.hip scatters per-env zombie counts and time limits (ZS_FLAG_ENV_PARAMS); a
@@ -27,6 +28,7 @@
 #include "zs_snapshot.hpp"
 #include "zs_record.hpp"
 #include "zs_mask.hpp"  // the mask launch's geometry (zs_describe); the kernel is k_mask.hip's
+#include "zs_entity_obs.hpp"  // the entity observation's layout and launcher; the kernel is k_entity_obs.hip's
 #include "zs_episode.hpp"  // the running part's columns (ZS_EP_RUN_COLS); the kernels are k_episode.hip's
 
 // ===========================================================================
@@ -92,6 +94,12 @@ struct zs_handle {
     uint64_t snap_fp = 0;  // snapshot_fingerprint() of the config (zs_snapshot.hpp)
     int32_t* d_envp_owner = nullptr;  // ZS_FLAG_ENV_PARAMS: zs_env_params_set's scratch, int32 [N], -1 between calls
     void* mask_bound = nullptr;  // zs_action_mask_bind: every zs_step ends with a mask launch into it
+    // the entity observation (zs_entity_obs.hpp): the objective list its kernel reads, and zs_entity_obs_bind's buffer
+    // and K values (every zs_step ends with a launch into it)
+    int32_t* d_obj_xy = nullptr;
+    void* ent_bound = nullptr;
+    int ent_kz = 0, ent_kp = 0;
+    const char* step_last = "";  // the launch that carried the tail of the last zs_step queued or captured (zs_describe)
     // ZS_FLAG_EPISODE_STATS: the statistics' arrays (k_episode.hip's argument; ep.run null without the flag) and the
     // [N] byte row the tick writes its reset flags to when the caller passes no reset_dev
     EpisodeArgs ep{};
@@ -371,6 +379,7 @@ static int create_static_tables(zs_handle* h, const zs_config* cfg, bool* rank_o
     TRY(dupload(h, &d.obst_kind, okind));
     TRY(dupload(h, &d.pspawn, ps));
     TRY(dupload(h, &d.zspawn, zs));
+    TRY(dupload(h, &h->d_obj_xy, packlist(m.objective_xy, m.n_objectives)));
     TRY(dupload(h, &d.agent_weapons, aw));
     TRY(dupload(h, &d.agent_codes, ac));
     TRY(dupload(h, &d.bot_types, bt));
@@ -836,15 +845,23 @@ extern "C" int zs_step(zs_handle* h, const int32_t* actions_dev, void* obs_dev, 
     if (d.fobs || !obs_dev) {
         const hipError_t le = launch_tail(s, d);
         if (le != hipSuccess) return tail_on_error(fail(ZS_EHIP, std::string("k_tail: ") + hipGetErrorString(le)));
+        h->step_last = "k_tail";
     } else {
         rc = launch_obs(h, d, obs_dev, nullptr, s);
         if (rc) return tail_on_error(rc);
+        h->step_last = obs_kernel_name(h->obs.full.kind);
     }
     // 4) a bound mask buffer (zs_action_mask_bind): the masks of the world the observations show, respawned
     //    zombies and reset envs included (the step's tail is done: nothing to undo when this launch fails)
     if (h->mask_bound) {
         const hipError_t me = launch_action_mask(s, d, nullptr, h->mask_bound);
         if (me != hipSuccess) return fail(ZS_EHIP, std::string("k_action_mask: ") + hipGetErrorString(me));
+    }
+    //    ... and a bound entity-observation buffer (zs_entity_obs_bind), of the same world
+    if (h->ent_bound) {
+        const EntityArgs g = {h->ent_kz, h->ent_kp, d.nobj, h->d_obj_xy};
+        const hipError_t ee = launch_entity_obs(s, d, g, nullptr, h->ent_bound);
+        if (ee != hipSuccess) return fail(ZS_EHIP, std::string("k_entity_obs: ") + hipGetErrorString(ee));
     }
     // 5) ZS_FLAG_EPISODE_STATS: the step's rewards and flags into the running returns, a finished episode latched
     //    and counted (the terminal world stays until the next call's reset work)
@@ -856,6 +873,17 @@ extern "C" int zs_step(zs_handle* h, const int32_t* actions_dev, void* obs_dev, 
     if (h->rn.body_col) {
         const hipError_t re = launch_render_track(s, h->rn, reset_dev, 0);
         if (re != hipSuccess) return fail(ZS_EHIP, std::string("k_render_track: ") + hipGetErrorString(re));
+    }
+    return ZS_OK;
+}
+
+// the cached step graphs hold the old launch sequence (a rare call: wait for the ones in flight first)
+static int drop_step_graphs(zs_handle* h) {
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipDeviceSynchronize());
+    for (auto& gs : h->gsets) {
+        HIPCHK(destroy_graphs(gs));
+        gs.used = 0;
     }
     return ZS_OK;
 }
@@ -883,14 +911,56 @@ extern "C" int zs_action_mask_bind(zs_handle* h, void* mask_dev_or_null) {
     int rc = mask_buffer_ok(mask_dev_or_null);
     if (rc) return rc;
     if (mask_dev_or_null == h->mask_bound) return ZS_OK;
-    // the cached step graphs hold the old launch sequence (a rare call: wait for the ones in flight first)
-    HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipDeviceSynchronize());
-    for (auto& gs : h->gsets) {
-        HIPCHK(destroy_graphs(gs));
-        gs.used = 0;
-    }
+    rc = drop_step_graphs(h);
+    if (rc) return rc;
     h->mask_bound = mask_dev_or_null;
+    return ZS_OK;
+}
+
+static int entity_args_ok(const void* out_dev, int kz, int kp) {
+    if (!ent_k_ok(kz, kp)) return fail(ZS_EINVAL, "entity observation: kz must be in 1..16 and kp in 0..16");
+    if (((uintptr_t)out_dev & 7u) != 0) return fail(ZS_EINVAL, "the entity-observation buffer must be 8-byte aligned");
+    return ZS_OK;
+}
+
+extern "C" int zs_entity_obs_layout(const zs_handle* h, int32_t kz, int32_t kp, int32_t out[8]) {
+    if (!h || !out) return fail(ZS_EINVAL, "null argument");
+    int rc = entity_args_ok(nullptr, kz, kp);
+    if (rc) return rc;
+    const EntLayout L = ent_layout(kz, kp);
+    const int32_t v[8] = {L.row_words, L.self, L.zombies, L.players, L.objective, L.rays, ZS_ENT_RAY_CAP, 2 * L.row_words};
+    std::memcpy(out, v, sizeof(v));
+    return ZS_OK;
+}
+
+// Entity observations of the current state (zs_entity_obs.hpp), int16 [N][A][ROW].  Viewer handles included: the
+// kernel reads what zs_obs_state_unpack fills and the static tables.
+extern "C" int zs_entity_obs(zs_handle* h, const uint8_t* env_mask_dev, int32_t kz, int32_t kp, void* out_dev, void* stream) {
+    if (!h || !out_dev) return fail(ZS_EINVAL, "null argument");
+    int rc = entity_args_ok(out_dev, kz, kp);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(hipSetDevice(h->device));
+    const EntityArgs g = {kz, kp, h->d.nobj, h->d_obj_xy};
+    HIPCHK(launch_entity_obs(s, h->d, g, env_mask_dev, out_dev));
+    return ZS_OK;
+}
+
+extern "C" int zs_entity_obs_bind(zs_handle* h, void* out_dev_or_null, int32_t kz, int32_t kp) {
+    if (!h) return fail(ZS_EINVAL, "null handle");
+    NOT_ON_VIEWER(h, "zs_entity_obs_bind");
+    if (out_dev_or_null) {
+        int rc = entity_args_ok(out_dev_or_null, kz, kp);
+        if (rc) return rc;
+    } else {
+        kz = kp = 0;
+    }
+    if (out_dev_or_null == h->ent_bound && kz == h->ent_kz && kp == h->ent_kp) return ZS_OK;
+    int rc = drop_step_graphs(h);
+    if (rc) return rc;
+    h->ent_bound = out_dev_or_null;
+    h->ent_kz = kz;
+    h->ent_kp = kp;
     return ZS_OK;
 }
 
@@ -1377,13 +1447,15 @@ extern "C" int zs_describe(zs_handle* h, char* buf, int32_t len) {
              "\"reset_lds\": %d, \"respawn\": \"%s\", \"tick_waves\": %d, \"rng_step\": %d, \"par_exec\": %d, "
              "\"obs_kernel_masked\": \"%s\", \"obs_encoders\": \"%s\", \"mask_kernel\": \"k_action_mask\", "
              "\"mask_grid\": %u, \"mask_block\": %d, \"mask_bound\": %d, \"env_params\": %d, \"episode_stats\": %d, "
-             "\"render\": %d, \"render_grid\": %d, \"render_block\": %d}",
+             "\"render\": %d, \"render_grid\": %d, \"render_block\": %d, \"entity_obs_bound\": %d, \"entity_kz\": %d, "
+             "\"entity_kp\": %d, \"step_tail_launch\": \"%s\"}",
              d.N, d.E, p.G, p.fused ? "k_step" : "k_tick", p.lds, p.resident, p.rw_cap,
              d.fobs ? "step launch" : obs_kernel_name(kf.kind), h->reset_side,
              p.reset_lds, p.defer_respawn ? "k_respawn" : "tick", p.tick_waves, p.rw_step,
              d.par_exec, obs_kernel_name(h->obs.masked.kind), obs_encoders_name(kf), zs_mask_grid(d.N), ZS_MASK_BLOCK,
              h->mask_bound ? 1 : 0, (d.flags & ZS_FLAG_ENV_PARAMS) ? 1 : 0, h->ep.run ? 1 : 0, h->rn.body_col ? 1 : 0,
-             h->rn.body_col ? h->rn.plan.bands : 0, h->rn.body_col ? ZS_RENDER_BLOCK : 0);
+             h->rn.body_col ? h->rn.plan.bands : 0, h->rn.body_col ? ZS_RENDER_BLOCK : 0,
+             h->ent_bound ? 1 : 0, h->ent_kz, h->ent_kp, h->step_last);
     return ZS_OK;
 }
 

@@ -19,6 +19,7 @@ SYMBOLS = ["zs_last_error", "zs_create", "zs_destroy", "zs_obs_shape", "zs_seed"
            "zs_obs_state_layout", "zs_obs_state_pack", "zs_obs_state_unpack",
            "zs_snapshot_layout", "zs_snapshot", "zs_restore",
            "zs_action_mask", "zs_action_mask_bind",
+           "zs_entity_obs_layout", "zs_entity_obs", "zs_entity_obs_bind",
            "zs_env_params_set", "zs_env_params_get", "zs_env_params_check",
            "zs_episode_stats_layout", "zs_episode_stats_get", "zs_episode_stats_clear",
            "zs_render_layout", "zs_render", "zs_render_sprites"]
@@ -84,6 +85,9 @@ def load_library(path=None):
     L.zs_restore.argtypes = [vp, vp, i32, i32, vp, vp, i32, vp]
     L.zs_action_mask.argtypes = [vp, vp, vp, vp]
     L.zs_action_mask_bind.argtypes = [vp, vp]
+    L.zs_entity_obs_layout.argtypes = [vp, i32, i32, C.POINTER(i32)]
+    L.zs_entity_obs.argtypes = [vp, vp, i32, i32, vp, vp]
+    L.zs_entity_obs_bind.argtypes = [vp, vp, i32, i32]
     L.zs_env_params_set.argtypes = [vp, vp, i32, vp, vp]
     L.zs_env_params_get.argtypes = [vp, i32, vp, vp]
     L.zs_env_params_check.argtypes = [vp, C.POINTER(C.c_uint32), vp]
@@ -151,7 +155,9 @@ def decode_death_log(words, n, E):
 class Engine(object):
     """N lock-step envs on one MI355X."""
 
-    def __init__(self, builder, device=None):
+    def __init__(self, builder, device=None, grid_obs=True):
+        """grid_obs=False: no grid observation is allocated or written (self.obs is None; every step, graphed step
+        and reset passes a null obs_dev): the engine of a learner on entity observations (bind_entity_obs)."""
         import torch
         if not torch.cuda.is_available():
             raise EngineUnavailable("no HIP device visible: the zombsole engine runs only on the GPU")
@@ -178,6 +184,7 @@ class Engine(object):
         dt = {_abi.DTYPE_I32: torch.int32, _abi.DTYPE_I64: torch.int64, _abi.DTYPE_I16: torch.int16}
         self.obs_dtype = dt[builder.cfg.obs_dtype]
         kw = dict(device=self.device)
+        self.grid_obs = bool(grid_obs)
         self.out = self.outputs()
         self.obs, self.rewards, self.done, self.trunc = self.out.obs, self.out.rewards, self.out.done, self.out.trunc
         self.listed, self.was_reset = self.out.listed, self.out.was_reset
@@ -187,6 +194,8 @@ class Engine(object):
         self.state_words = int(n.value)
         self.n_discrete = 7 if self.multi else 6
         self.masks = None  # the bound action-mask tensor (bind_action_masks), uint8 [N, A, 8]
+        self.entities = None  # the bound entity-observation tensor (bind_entity_obs), int16 [N, A, ROW]
+        self.entity_k = None  # its (kz, kp)
 
     def close(self):
         if getattr(self, "h", None) and self.h.value:
@@ -230,7 +239,10 @@ class Engine(object):
                             _ptr(o.trunc), _ptr(o.listed), _ptr(o.was_reset), self._stream())
         if rc:
             _raise(self.L, rc, "zs_step")
-        return o.obs[:self.N], o.rewards[:self.N], o.done[:self.N], o.trunc[:self.N]
+        return self._obs_rows(o), o.rewards[:self.N], o.done[:self.N], o.trunc[:self.N]
+
+    def _obs_rows(self, o):
+        return None if o.obs is None else o.obs[:self.N]
 
     def step_graph(self, step0, n_discrete, out=None, steps=1, actions=None):
         """gen_actions(t, n_discrete) + step() as one replayed hipGraph (t = step0 on the first call,
@@ -250,7 +262,7 @@ class Engine(object):
                                         _ptr(o.was_reset), self._stream())
         if rc:
             _raise(self.L, rc, "zs_step_graph")
-        return o.obs[:self.N], o.rewards[:self.N], o.done[:self.N], o.trunc[:self.N]
+        return self._obs_rows(o), o.rewards[:self.N], o.done[:self.N], o.trunc[:self.N]
 
     def step_graphed(self, actions=None, out=None):
         """step(actions) as one replayed hipGraph launch (zs_step_graph with n_discrete = 0): the
@@ -264,6 +276,8 @@ class Engine(object):
         unpack_obs_state) into `out` (default: self.obs), a tensor of the observations' dtype with at least
         N rows of obs_shape."""
         o = self.obs if out is None else out
+        if o is None:
+            raise ValueError("observe: this engine keeps no grid observations (grid_obs=False); pass out=")
         if out is not None:
             if (o.dtype != self.obs_dtype or o.device != self.device or not o.is_contiguous() or
                     tuple(o.shape[1:]) != tuple(self.obs_shape) or o.shape[0] < self.N):
@@ -309,6 +323,70 @@ class Engine(object):
         if rc:
             _raise(self.L, rc, "zs_action_mask_bind")
         self.masks = buf
+        return buf
+
+    # -- entity observations (zs_entity_obs*): per agent its own values, the K nearest zombies and players, the nearest
+    # objective and four rays, int16 [N, A, ROW] ------------------------------------------------------------------
+    def entity_layout(self, kz=None, kp=None):
+        """zs_entity_obs_layout as a dict: "row_words", the word offsets "self", "zombies", "players", "objective",
+        "rays", "ray_cap" and "row_bytes", with "kz" and "kp" (default: the bound tensor's)."""
+        kz, kp = self._entity_k(kz, kp)
+        out = (C.c_int32 * 8)()
+        rc = self.L.zs_entity_obs_layout(self.h, kz, kp, out)
+        if rc:
+            _raise(self.L, rc, "zs_entity_obs_layout")
+        L = dict(zip(_abi.ENTITY_LAYOUT_KEYS, (int(v) for v in out)))
+        L.update(kz=kz, kp=kp)
+        return L
+
+    def _entity_k(self, kz, kp):
+        if kz is None and kp is None and self.entity_k is not None:
+            return self.entity_k
+        if kz is None or kp is None:
+            raise ValueError("entity observations: kz and kp are needed (no tensor is bound)")
+        return int(kz), int(kp)
+
+    def _check_entities(self, t, kz, kp, what):
+        L = _abi.entity_layout(kz, kp)  # ValueError on bad K values
+        if (t.dtype != self.torch.int16 or t.device != self.device or not t.is_contiguous() or t.data_ptr() % 8 or
+                tuple(t.shape) != (self.N, self.A, L["row_words"])):
+            raise ValueError("%s: entity observations are a contiguous, 8-byte aligned int16 tensor [%d, %d, %d] on %s"
+                             % (what, self.N, self.A, L["row_words"], self.device))
+
+    def entity_obs(self, mask=None, out=None, kz=None, kp=None):
+        """The entity observations of the current state, int16 [N, A, 16 + 4 (kz + kp)] (zs_entity_obs; the layout:
+        entity_layout, libzombsole_amd/entity_obs.py).  Envs where the uint8 device tensor `mask` is zero keep their
+        bytes.  Into `out` when given, else into the bound tensor (with its kz, kp), else into a tensor this call
+        allocates (zeroed)."""
+        kz, kp = self._entity_k(kz, kp)
+        o = out
+        if o is None and self.entities is not None and (kz, kp) == self.entity_k:
+            o = self.entities
+        if o is None:
+            o = self.torch.zeros((self.N, self.A, _abi.entity_layout(kz, kp)["row_words"]), dtype=self.torch.int16,
+                                 device=self.device)
+        self._check_entities(o, kz, kp, "entity_obs")
+        rc = self.L.zs_entity_obs(self.h, _ptr(mask), kz, kp, _ptr(o), self._stream())
+        if rc:
+            _raise(self.L, rc, "zs_entity_obs")
+        return o
+
+    def bind_entity_obs(self, buf=True, kz=4, kp=1):
+        """Bind `buf` (True: a new tensor; None / False: unbind) so that every step(), step_graph() and
+        step_graphed() ends with an entity-observation launch into it (zs_entity_obs_bind); self.entities is the
+        bound tensor and self.entity_k its (kz, kp)."""
+        if buf is True:
+            buf = self.torch.zeros((self.N, self.A, _abi.entity_layout(kz, kp)["row_words"]), dtype=self.torch.int16,
+                                   device=self.device)
+        elif buf is False:
+            buf = None
+        if buf is not None:
+            self._check_entities(buf, kz, kp, "bind_entity_obs")
+        rc = self.L.zs_entity_obs_bind(self.h, _ptr(buf), int(kz) if buf is not None else 0, int(kp) if buf is not None else 0)
+        if rc:
+            _raise(self.L, rc, "zs_entity_obs_bind")
+        self.entities = buf
+        self.entity_k = (int(kz), int(kp)) if buf is not None else None
         return buf
 
     # -- observation-state records (zs_obs_state_*): what the encoders read of an env, a fraction of its observation
@@ -598,7 +676,7 @@ class Engine(object):
     def describe(self):
         """The launch configuration the engine chose (zs_describe), as a dict."""
         import json
-        buf = C.create_string_buffer(1024)
+        buf = C.create_string_buffer(2048)
         rc = self.L.zs_describe(self.h, buf, len(buf))
         if rc:
             _raise(self.L, rc, "zs_describe")
@@ -779,12 +857,14 @@ class StepOutputs(object):
         A = eng.A
         self.rows = rows
         nb = rows * self.row_bytes(eng)
+        grid = getattr(eng, "grid_obs", True)
         if obs is not None:
+            assert grid, "an engine built with grid_obs=False writes no observations"
             assert obs.shape == (rows,) + tuple(eng.obs_shape) and obs.dtype == eng.obs_dtype and obs.is_contiguous()
         if flat is not None:
             assert flat.dim() == 1 and flat.numel() >= nb and flat.dtype == torch.uint8
             assert flat.is_contiguous() and flat.storage_offset() % 8 == 0
-        self.obs = obs if obs is not None else torch.zeros((rows,) + eng.obs_shape, dtype=eng.obs_dtype, **kw)
+        self.obs = obs if obs is not None or not grid else torch.zeros((rows,) + eng.obs_shape, dtype=eng.obs_dtype, **kw)
         self.flat = flat if flat is not None else torch.zeros(nb, dtype=torch.uint8, **kw)
         o = 8 * R * rows
         self.rewards = self.flat[:o].view(torch.float64).view(rows, R)

@@ -67,7 +67,8 @@ class BatchedZombsole(object):
                  observation_scope="world", observation_position_encoding="simple", agent_weapon="rifle",
                  observation_surroundings_width=21, observation_position_encoding_style="channels",
                  agent_weapons="rifle", obs_dtype=None, autoreset=True, device=None, lanes_per_env=0,
-                 action_masks=False, env_params=False, episode_stats=False, render=False):
+                 action_masks=False, env_params=False, episode_stats=False, render=False, entity_obs=None,
+                 grid_obs=True):
         if surface == "single":
             b = _abi.single_env_config(num_envs, rules_name, player_names, map_name, agent_id, initial_zombies,
                                        minimum_zombies, observation_scope, observation_position_encoding,
@@ -83,7 +84,9 @@ class BatchedZombsole(object):
         else:
             raise ValueError("surface must be 'single' or 'multi'")
         self.surface = surface
-        self.engine = Engine(b, device=device)
+        if not grid_obs and entity_obs is None:
+            raise ValueError("grid_obs=False needs entity_obs=(kz, kp): the env would have no observation")
+        self.engine = Engine(b, device=device, grid_obs=grid_obs)
         self.torch = self.engine.torch
         self.num_envs = int(num_envs)
         self.env0 = int(env0)
@@ -95,6 +98,20 @@ class BatchedZombsole(object):
         # restore, clone and load_checkpoint launch it themselves
         if action_masks:
             self.engine.bind_action_masks()
+        # entity_obs=(kz, kp): an entity-observation tensor bound the same way, refreshed at the same places.
+        # grid_obs=False: no grid observation is allocated or written; the entity tensor is the observation
+        if entity_obs is not None:
+            self.engine.bind_entity_obs(True, int(entity_obs[0]), int(entity_obs[1]))
+
+    @property
+    def entity_obs(self):
+        """int16 [N, A, 16 + 4 (kz + kp)]: the engine's bound entity observations (libzombsole_amd/entity_obs.py) of
+        the world self.obs shows.  Valid after every reset, step, restore / clone and load_checkpoint.  None without
+        entity_obs=(kz, kp)."""
+        return self.engine.entities
+
+    def _observation(self):
+        return self.engine.obs if self.engine.grid_obs else self.engine.entities
 
     @property
     def action_masks(self):
@@ -164,10 +181,12 @@ class BatchedZombsole(object):
         return self.engine.listed
 
     def reset(self, mask=None):
-        obs = self.engine.reset(mask)
+        self.engine.reset(mask)
         if self.engine.masks is not None:
             self.engine.action_mask(mask)
-        return obs
+        if self.engine.entities is not None:
+            self.engine.entity_obs(mask)
+        return self._observation()
 
     def discrete_to_triples(self, ids):
         """Discrete(6)/(7) ids [N, A] (gym_env.py:328-351, gym/multiagent_env.py:259-285) -> [N, A, 3]."""
@@ -191,11 +210,15 @@ class BatchedZombsole(object):
         if not graph:
             if actions.dtype != t.int32 or not actions.is_contiguous():
                 actions = actions.to(t.int32).contiguous()
-            return self.engine.step(actions)
+            return self._stepped(self.engine.step(actions))
         buf = self.engine.actions
         if actions.data_ptr() != buf.data_ptr():
             buf.copy_(actions)
-        return self.engine.step_graphed(buf)
+        return self._stepped(self.engine.step_graphed(buf))
+
+    def _stepped(self, res):
+        # grid_obs=False: the step's observation is the bound entity tensor
+        return res if self.engine.grid_obs else (self.engine.entities,) + tuple(res[1:])
 
     def sample_actions(self, step):
         """The bench/parity uniform policy, generated on device (zs_gen_actions)."""
@@ -208,10 +231,11 @@ class BatchedZombsole(object):
 
     def restore(self, snap, src=None, dst=None, observe=True, check=True):
         """Record src[k] of `snap` (default: k) into env dst[k] (default: k); see Engine.restore.  observe=True
-        re-encodes the written envs (a masked observe) and returns self.obs, whose other rows are untouched."""
+        re-encodes the written envs (a masked observe) and returns self.obs, whose other rows are untouched (with
+        grid_obs=False: the entity tensor, which is refreshed whenever one is bound)."""
         eng, t = self.engine, self.torch
         eng.restore(snap, src, dst, check=check)
-        if not observe and self.engine.masks is None:
+        if not observe and self.engine.masks is None and self.engine.entities is None:
             return None
         mask = t.zeros(eng.N, dtype=t.uint8, device=eng.device)
         if dst is None:
@@ -222,7 +246,11 @@ class BatchedZombsole(object):
             mask[d[(d >= 0) & (d < eng.N)]] = 1
         if self.engine.masks is not None:  # the written envs' action masks, beside their observations
             eng.action_mask(mask)
-        return eng.observe(mask) if observe else None
+        if self.engine.entities is not None:
+            eng.entity_obs(mask)
+        if not observe:
+            return None
+        return eng.observe(mask) if eng.grid_obs else eng.entities
 
     def clone(self, src, dst, observe=True):
         """Env dst[k] becomes a copy of env src[k] (fork; sources may repeat).  The copy goes through records in a
