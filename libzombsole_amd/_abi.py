@@ -125,8 +125,19 @@ def snapshot_layout(E, O, DW, OW, A, env_params=False, episode_R=0, body_bytes=0
 
 _M64 = (1 << 64) - 1
 
-
+# The words of the six layout calls' out[] (include/zombsole_mi355x.h), by position: Engine._layout zips them with the
+# call's output.  None: a reserved word.  A snapshot record's fingerprint comes as two 32-bit halves.
 ENTITY_LAYOUT_KEYS = ("row_words", "self", "zombies", "players", "objective", "rays", "ray_cap", "row_bytes")
+LAYOUT_KEYS = {
+    "zs_obs_state_layout": ("rec_bytes",) + OBS_STATE_SECTIONS + ("pad", "hp_bytes"),
+    "zs_snapshot_layout": ("rec_bytes",) + SNAPSHOT_SECTIONS + ("pad", "fingerprint_lo", "fingerprint_hi", "nscal", "ring_words",
+                                                                "env_params"),
+    "zs_entity_obs_layout": ENTITY_LAYOUT_KEYS,
+    "zs_episode_stats_layout": ("R", "last_words", "tot_words", "ep_run", "ep_bytes", None, None, None),
+    "zs_render_layout": ("height", "width", "frame_bytes", "cell", "mask", "palette", "body_bytes", "body_col"),
+    "zs_host_layout": ("words", "rew", "alog", "dlog", "state", "obs", "obs_bytes", "R"),
+}
+
 ENTITY_KMAX, ENTITY_RAY_CAP = 16, 16
 
 
@@ -199,6 +210,65 @@ class zs_config(C.Structure):
                 ("obs_width", C.c_int32), ("obs_dtype", C.c_int32),
                 ("max_episode_steps", C.c_int32), ("flags", C.c_uint32), ("lanes_per_env", C.c_int32),
                 ("launch", C.POINTER(zs_launch))]
+
+
+# Every call of the C ABI (include/zombsole_mi355x.h, in its order) with its argtypes; engine.load_library binds them.
+# The restype is c_int (a ZS_* status) for all but zs_last_error, which returns the message as c_char_p.
+# tests/test_abi.py holds the names and the parameter counts to the header.
+_vp, _i32, _u64 = C.c_void_p, C.c_int32, C.c_uint64
+_pi32, _pu32 = C.POINTER(C.c_int32), C.POINTER(C.c_uint32)
+ABI = {
+    "zs_last_error": [],
+    "zs_create": [_vp, C.c_int, C.POINTER(_vp)],
+    "zs_destroy": [_vp],
+    "zs_obs_shape": [_vp, _pi32],
+    "zs_seed": [_vp, _i32, _i32, C.POINTER(_u64), _vp],
+    "zs_reset": [_vp, _vp, _vp, _vp],
+    "zs_observe": [_vp, _vp, _vp, _vp],
+    "zs_step": [_vp] * 9,
+    "zs_gen_actions": [_vp, _u64, _i32, _vp, _vp],
+    "zs_step_graph": [_vp, _u64, _i32] + [_vp] * 8,
+    "zs_step_graph_n": [_vp, _u64, _i32, _i32] + [_vp] * 8,
+    "zs_state_size": [_vp, _pi32],
+    "zs_get_state": [_vp, _i32, _vp, _vp],
+    "zs_set_state": [_vp, _i32, _vp, _vp],
+    "zs_get_rng": [_vp, _i32, _vp, _vp],
+    "zs_set_rng": [_vp, _i32, _vp, _vp],
+    "zs_overflow": [_vp, _pu32, _i32, _vp],
+    "zs_obs_state_layout": [_vp, _pi32],
+    "zs_obs_state_pack": [_vp, _vp, _vp],
+    "zs_obs_state_unpack": [_vp, _vp, _i32, _i32, _i32, _vp],
+    "zs_snapshot_layout": [_vp, _pi32],
+    "zs_snapshot": [_vp, _vp, _i32, _vp, _vp],
+    "zs_restore": [_vp, _vp, _i32, _i32, _vp, _vp, _i32, _vp],
+    "zs_action_mask": [_vp, _vp, _vp, _vp],
+    "zs_action_mask_bind": [_vp, _vp],
+    "zs_entity_obs_layout": [_vp, _i32, _i32, _pi32],
+    "zs_entity_obs": [_vp, _vp, _i32, _i32, _vp, _vp],
+    "zs_entity_obs_bind": [_vp, _vp, _i32, _i32],
+    "zs_env_params_set": [_vp, _vp, _i32, _vp, _vp],
+    "zs_env_params_get": [_vp, _i32, _vp, _vp],
+    "zs_env_params_check": [_vp, _pu32, _vp],
+    "zs_episode_stats_layout": [_vp, _pi32],
+    "zs_episode_stats_get": [_vp] * 8,
+    "zs_episode_stats_clear": [_vp, _vp, _vp],
+    "zs_render_layout": [_vp, _pi32],
+    "zs_render": [_vp, _vp, _i32, _vp, _i32, _vp],
+    "zs_render_sprites": [_vp, _vp, _vp],
+    "zs_profile": [_vp, _i32],
+    "zs_profile_read": [_vp, C.POINTER(C.c_double)],
+    "zs_describe": [_vp, C.c_char_p, _i32],
+    "zs_debug_lists": [_vp, _pi32, _vp],
+    "zs_death_log": [_vp, _i32, _pi32, _i32, _pi32, _vp],
+    "zs_action_log": [_vp, _i32, _pi32, _i32, _pi32, _vp],
+    "zs_host_layout": [_vp, _pi32],
+    "zs_host_step": [_vp, _vp, _vp, _vp, _vp],
+    "zs_host_reset": [_vp, _vp, _vp, _vp],
+    "zs_host_observe": [_vp, _vp, _vp],
+    "zs_debug_stamps": [_vp, _vp, _vp, _i32],
+    "zs_debug_timeline": [_vp, _vp, _i32],
+    "zs_debug_stamps_wg": [_vp, _vp, _i32, _i32],
+}
 
 
 def rules_id(rules_name):

@@ -57,6 +57,19 @@ static hipError_t obs_attr(int dtype, int kind, int nobs, int patched, int bytes
         if (_e != hipSuccess) return fail(ZS_EHIP, std::string(#x ": ") + hipGetErrorString(_e)); \
     } while (0)
 
+// a step that returns a ZS_* status and has set the message: a failure is the caller's result
+#define TRY(x)             \
+    do {                   \
+        int _r = (x);      \
+        if (_r) return _r; \
+    } while (0)
+
+// a kernel launch's status under the kernel's name: "k_x: <hip error string>"
+static int launched(const char* name, hipError_t e) {
+    return e == hipSuccess ? ZS_OK : fail(ZS_EHIP, std::string(name) + ": " + hipGetErrorString(e));
+}
+#define LAUNCHCHK(name, x) TRY(launched((name), (x)))
+
 struct zs_handle {
     zs_config cfg;
     zs_launch ov;   // launch overrides (zs_config.launch, zeroed when NULL)
@@ -142,8 +155,7 @@ template <typename F>
 static int timed_launch(zs_handle* h, hipStream_t s, EventList& list, const char* what, F launch) {
     int i0 = -1, i1 = -1;
     if (h->prof) HIPCHK(hipEventRecord(prof_event(h, &i0), s));
-    const hipError_t e = launch();
-    if (e != hipSuccess) return fail(ZS_EHIP, std::string(what) + ": " + hipGetErrorString(e));
+    LAUNCHCHK(what, launch());
     if (h->prof) {
         HIPCHK(hipEventRecord(prof_event(h, &i1), s));
         list.push_back({i0, i1});
@@ -190,11 +202,29 @@ static int viewer_refused(const zs_handle* h, const char* call) {
     if (!(h->cfg.flags & ZS_FLAG_VIEWER)) return ZS_OK;
     return fail(ZS_ESTATE, std::string(call) + ": not on a viewer handle (ZS_FLAG_VIEWER)");
 }
-#define NOT_ON_VIEWER(h, call)                  \
-    do {                                        \
-        int _v = viewer_refused((h), (call));   \
-        if (_v) return _v;                      \
-    } while (0)
+#define NOT_ON_VIEWER(h, call) TRY(viewer_refused((h), (call)))
+
+// an entry point's prologue: the caller's stream, and the handle's device current
+static int enter(const zs_handle* h, void* stream, hipStream_t* s) {
+    *s = (hipStream_t)stream;
+    HIPCHK(hipSetDevice(h->device));
+    return ZS_OK;
+}
+#define ENTER(h, stream, s) \
+    hipStream_t s;          \
+    TRY(enter((h), (stream), &s))
+
+// a call of a feature the handle was created without
+static int need_flag(const char* call, bool have, const char* flag) {
+    if (have) return ZS_OK;
+    return fail(ZS_ESTATE, std::string(call) + ": the handle was created without " + flag);
+}
+
+// a record buffer (observation-state or snapshot records) starts at a 16-byte boundary
+static int rec_aligned(const void* rec_dev) {
+    if ((uintptr_t)rec_dev & 15) return fail(ZS_EINVAL, "rec_dev must be 16-byte aligned");
+    return ZS_OK;
+}
 
 template <typename T>
 static int dalloc(zs_handle* h, T** p, size_t count) {
@@ -209,8 +239,7 @@ static int dalloc(zs_handle* h, T** p, size_t count) {
 
 template <typename T>
 static int dupload(zs_handle* h, T** p, const std::vector<T>& v) {
-    int rc = dalloc(h, p, v.size());
-    if (rc) return rc;
+    TRY(dalloc(h, p, v.size()));
     if (!v.empty()) HIPCHK(hipMemcpy(*p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
     return ZS_OK;
 }
@@ -304,12 +333,6 @@ struct HandleOwner {
         delete h;
     }
 };
-
-#define TRY(x)             \
-    do {                   \
-        int _r = (x);      \
-        if (_r) return _r; \
-    } while (0)
 
 // zs_create: the static tables of the map and the config, uploaded; *rank_order: the obstacles are in
 // row-major order
@@ -559,8 +582,7 @@ static int create_step_plan(zs_handle* h) {
 extern "C" int zs_create(const zs_config* cfg, int device, zs_handle** out) {
     if (!cfg || !out) return fail(ZS_EINVAL, "null argument");
     *out = nullptr;
-    int rc = validate(cfg);
-    if (rc) return rc;
+    TRY(validate(cfg));
     if ((cfg->flags & ZS_FLAG_ENV_PARAMS) && (cfg->flags & ZS_FLAG_VIEWER))  // nothing resets or steps a viewer's envs
         return fail(ZS_ESTATE, "zs_create: ZS_FLAG_ENV_PARAMS: not on a viewer handle (ZS_FLAG_VIEWER)");
     if ((cfg->flags & ZS_FLAG_EPISODE_STATS) && (cfg->flags & ZS_FLAG_VIEWER))
@@ -642,7 +664,6 @@ extern "C" int zs_create(const zs_config* cfg, int device, zs_handle** out) {
     owner.h = nullptr;
     return ZS_OK;
 }
-#undef TRY
 
 extern "C" int zs_obs_shape(const zs_handle* h, int32_t out[4]) {
     if (!h || !out) return fail(ZS_EINVAL, "null argument");
@@ -664,8 +685,7 @@ extern "C" int zs_seed(zs_handle* h, int32_t env0, int32_t n, const uint64_t* se
 static int seed_envs(zs_handle* h, int32_t env0, int32_t n, const uint64_t* seeds_host, void* stream) {
     if (env0 < 0 || n < 0 || env0 + n > h->d.N) return fail(ZS_EINVAL, "env range out of bounds");
     if (n == 0) return ZS_OK;
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHK(hipSetDevice(h->device));
+    ENTER(h, stream, s);
     HIPCHK(hipMemcpyAsync(h->d_seedbuf, seeds_host, sizeof(uint64_t) * n, hipMemcpyHostToDevice, s));
     HIPCHK(launch_seed(s, h->d, env0, n, h->d_seedbuf));
     HIPCHK(hipStreamSynchronize(s));  // seeds_host may be freed by the caller on return
@@ -725,8 +745,7 @@ static int launch_respawn(zs_handle* h, const Dev& d, hipStream_t s) {
 // zs_reset's launches, queued on s (the caller synchronises and reads h->d_err)
 static int queue_reset(zs_handle* h, const uint8_t* env_mask_dev, void* obs_dev, hipStream_t s) {
     HIPCHK(hipMemsetAsync(h->d_err, 0, sizeof(int), s));
-    int rc = launch_reset(h, h->d, 0, env_mask_dev, nullptr, s);
-    if (rc) return rc;
+    TRY(launch_reset(h, h->d, 0, env_mask_dev, nullptr, s));
     // the pending-reset list must hold exactly the envs still pending: drop the ones just rebuilt
     {
         int p = h->rpar, q = 1 - p;
@@ -752,12 +771,10 @@ static int queue_reset(zs_handle* h, const uint8_t* env_mask_dev, void* obs_dev,
 extern "C" int zs_reset(zs_handle* h, const uint8_t* env_mask_dev, void* obs_dev, void* stream) {
     if (!h) return fail(ZS_EINVAL, "null handle");
     NOT_ON_VIEWER(h, "zs_reset");
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHK(hipSetDevice(h->device));
-    int rc = queue_reset(h, env_mask_dev, obs_dev, s);
-    if (rc) return rc;
+    ENTER(h, stream, s);
+    TRY(queue_reset(h, env_mask_dev, obs_dev, s));
     int err;
-    if ((rc = read_error_word(h, s, &err))) return rc;
+    TRY(read_error_word(h, s, &err));
     return reset_result(err);
 }
 
@@ -765,8 +782,7 @@ extern "C" int zs_reset(zs_handle* h, const uint8_t* env_mask_dev, void* obs_dev
 // current state of the masked envs, e.g. after a zs_set_state poke.
 extern "C" int zs_observe(zs_handle* h, const uint8_t* env_mask_dev, void* obs_dev, void* stream) {
     if (!h || !obs_dev) return fail(ZS_EINVAL, "null argument");
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHK(hipSetDevice(h->device));
+    ENTER(h, stream, s);
     return launch_obs(h, h->d, obs_dev, env_mask_dev, s);
 }
 
@@ -774,8 +790,7 @@ extern "C" int zs_step(zs_handle* h, const int32_t* actions_dev, void* obs_dev, 
                        uint8_t* trunc_dev, uint8_t* listed_dev, uint8_t* reset_dev, void* stream) {
     if (!h || !actions_dev || !rewards_dev || !done_dev || !trunc_dev) return fail(ZS_EINVAL, "null argument");
     NOT_ON_VIEWER(h, "zs_step");
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHK(hipSetDevice(h->device));
+    ENTER(h, stream, s);
     // ZS_FLAG_EPISODE_STATS: the update rule reads the tick's reset flags, so a caller that wants none gets the
     // handle's own row (one row whatever the caller's buffers: the step graphs stay keyed on the caller's pointers)
     if ((h->ep.run || h->rn.body_col) && !reset_dev) reset_dev = h->d_ep_reset;
@@ -798,8 +813,7 @@ extern "C" int zs_step(zs_handle* h, const int32_t* actions_dev, void* obs_dev, 
         // no gap: 8 192 envs 110 -> 117 M env-steps/s)
         if (h->graph_pol && side)
             HIPCHK(launch_gen_actions_ctr(s, h->d, (const uint64_t*)h->d_gstep, h->graph_pol, (int32_t*)actions_dev));
-        rc = launch_reset(h, h->d, 1, nullptr, h->d.fobs ? obs_dev : nullptr, rs);
-        if (rc) return rc;
+        TRY(launch_reset(h, h->d, 1, nullptr, h->d.fobs ? obs_dev : nullptr, rs));
         if (side) HIPCHK(hipEventRecord(h->ev_rjoin, h->s_reset));
     }
     // this step's Dev: the handle's (whose pol_* and tail_* stay null) with the policy the step launch generates
@@ -817,9 +831,8 @@ extern "C" int zs_step(zs_handle* h, const int32_t* actions_dev, void* obs_dev, 
     // sequence standalone without a fault, profiles/r03_graphprobe_fork.log.)  Every list index is
     // bounds-checked in the kernels.
     const int p = h->rpar;
-    rc = launch_tick(h, d, actions_dev, rewards_dev, done_dev, trunc_dev, listed_dev, reset_dev, h->d_rlist[q],
-                     h->d_rcount + q, obs_dev, s);
-    if (rc) return rc;
+    TRY(launch_tick(h, d, actions_dev, rewards_dev, done_dev, trunc_dev, listed_dev, reset_dev, h->d_rlist[q],
+                    h->d_rcount + q, obs_dev, s));
     h->rpar = q;
     // a launch failing after the tick was queued: the step's tail (the counter protocol above) is done
     // here instead, so the next step does not append after stale counts (not while capturing: a failed
@@ -843,8 +856,8 @@ extern "C" int zs_step(zs_handle* h, const int32_t* actions_dev, void* obs_dev, 
     d.tail_cnt1 = d.defer_respawn ? d.resp_count : nullptr;
     d.tail_step = h->graph_pol ? h->d_gstep : nullptr;
     if (d.fobs || !obs_dev) {
-        const hipError_t le = launch_tail(s, d);
-        if (le != hipSuccess) return tail_on_error(fail(ZS_EHIP, std::string("k_tail: ") + hipGetErrorString(le)));
+        rc = launched("k_tail", launch_tail(s, d));
+        if (rc) return tail_on_error(rc);
         h->step_last = "k_tail";
     } else {
         rc = launch_obs(h, d, obs_dev, nullptr, s);
@@ -853,27 +866,17 @@ extern "C" int zs_step(zs_handle* h, const int32_t* actions_dev, void* obs_dev, 
     }
     // 4) a bound mask buffer (zs_action_mask_bind): the masks of the world the observations show, respawned
     //    zombies and reset envs included (the step's tail is done: nothing to undo when this launch fails)
-    if (h->mask_bound) {
-        const hipError_t me = launch_action_mask(s, d, nullptr, h->mask_bound);
-        if (me != hipSuccess) return fail(ZS_EHIP, std::string("k_action_mask: ") + hipGetErrorString(me));
-    }
+    if (h->mask_bound) LAUNCHCHK("k_action_mask", launch_action_mask(s, d, nullptr, h->mask_bound));
     //    ... and a bound entity-observation buffer (zs_entity_obs_bind), of the same world
     if (h->ent_bound) {
         const EntityArgs g = {h->ent_kz, h->ent_kp, d.nobj, h->d_obj_xy};
-        const hipError_t ee = launch_entity_obs(s, d, g, nullptr, h->ent_bound);
-        if (ee != hipSuccess) return fail(ZS_EHIP, std::string("k_entity_obs: ") + hipGetErrorString(ee));
+        LAUNCHCHK("k_entity_obs", launch_entity_obs(s, d, g, nullptr, h->ent_bound));
     }
     // 5) ZS_FLAG_EPISODE_STATS: the step's rewards and flags into the running returns, a finished episode latched
     //    and counted (the terminal world stays until the next call's reset work)
-    if (h->ep.run) {
-        const hipError_t ee = launch_episode_stats(s, h->ep, rewards_dev, done_dev, trunc_dev, reset_dev);
-        if (ee != hipSuccess) return fail(ZS_EHIP, std::string("k_episode_stats: ") + hipGetErrorString(ee));
-    }
+    if (h->ep.run) LAUNCHCHK("k_episode_stats", launch_episode_stats(s, h->ep, rewards_dev, done_dev, trunc_dev, reset_dev));
     // 6) ZS_FLAG_RENDER: the step's death log into the body colours; a reset env's row cleared
-    if (h->rn.body_col) {
-        const hipError_t re = launch_render_track(s, h->rn, reset_dev, 0);
-        if (re != hipSuccess) return fail(ZS_EHIP, std::string("k_render_track: ") + hipGetErrorString(re));
-    }
+    if (h->rn.body_col) LAUNCHCHK("k_render_track", launch_render_track(s, h->rn, reset_dev, 0));
     return ZS_OK;
 }
 
@@ -897,10 +900,8 @@ static int mask_buffer_ok(const void* mask_dev) {
 // what zs_obs_state_unpack fills (pos, present, weapon, obstacle presence) and the static cell map.
 extern "C" int zs_action_mask(zs_handle* h, const uint8_t* env_mask_dev, void* mask_dev, void* stream) {
     if (!h || !mask_dev) return fail(ZS_EINVAL, "null argument");
-    int rc = mask_buffer_ok(mask_dev);
-    if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHK(hipSetDevice(h->device));
+    TRY(mask_buffer_ok(mask_dev));
+    ENTER(h, stream, s);
     HIPCHK(launch_action_mask(s, h->d, env_mask_dev, mask_dev));
     return ZS_OK;
 }
@@ -908,11 +909,9 @@ extern "C" int zs_action_mask(zs_handle* h, const uint8_t* env_mask_dev, void* m
 extern "C" int zs_action_mask_bind(zs_handle* h, void* mask_dev_or_null) {
     if (!h) return fail(ZS_EINVAL, "null handle");
     NOT_ON_VIEWER(h, "zs_action_mask_bind");
-    int rc = mask_buffer_ok(mask_dev_or_null);
-    if (rc) return rc;
+    TRY(mask_buffer_ok(mask_dev_or_null));
     if (mask_dev_or_null == h->mask_bound) return ZS_OK;
-    rc = drop_step_graphs(h);
-    if (rc) return rc;
+    TRY(drop_step_graphs(h));
     h->mask_bound = mask_dev_or_null;
     return ZS_OK;
 }
@@ -925,8 +924,7 @@ static int entity_args_ok(const void* out_dev, int kz, int kp) {
 
 extern "C" int zs_entity_obs_layout(const zs_handle* h, int32_t kz, int32_t kp, int32_t out[8]) {
     if (!h || !out) return fail(ZS_EINVAL, "null argument");
-    int rc = entity_args_ok(nullptr, kz, kp);
-    if (rc) return rc;
+    TRY(entity_args_ok(nullptr, kz, kp));
     const EntLayout L = ent_layout(kz, kp);
     const int32_t v[8] = {L.row_words, L.self, L.zombies, L.players, L.objective, L.rays, ZS_ENT_RAY_CAP, 2 * L.row_words};
     std::memcpy(out, v, sizeof(v));
@@ -937,10 +935,8 @@ extern "C" int zs_entity_obs_layout(const zs_handle* h, int32_t kz, int32_t kp, 
 // kernel reads what zs_obs_state_unpack fills and the static tables.
 extern "C" int zs_entity_obs(zs_handle* h, const uint8_t* env_mask_dev, int32_t kz, int32_t kp, void* out_dev, void* stream) {
     if (!h || !out_dev) return fail(ZS_EINVAL, "null argument");
-    int rc = entity_args_ok(out_dev, kz, kp);
-    if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHK(hipSetDevice(h->device));
+    TRY(entity_args_ok(out_dev, kz, kp));
+    ENTER(h, stream, s);
     const EntityArgs g = {kz, kp, h->d.nobj, h->d_obj_xy};
     HIPCHK(launch_entity_obs(s, h->d, g, env_mask_dev, out_dev));
     return ZS_OK;
@@ -950,14 +946,12 @@ extern "C" int zs_entity_obs_bind(zs_handle* h, void* out_dev_or_null, int32_t k
     if (!h) return fail(ZS_EINVAL, "null handle");
     NOT_ON_VIEWER(h, "zs_entity_obs_bind");
     if (out_dev_or_null) {
-        int rc = entity_args_ok(out_dev_or_null, kz, kp);
-        if (rc) return rc;
+        TRY(entity_args_ok(out_dev_or_null, kz, kp));
     } else {
         kz = kp = 0;
     }
     if (out_dev_or_null == h->ent_bound && kz == h->ent_kz && kp == h->ent_kp) return ZS_OK;
-    int rc = drop_step_graphs(h);
-    if (rc) return rc;
+    TRY(drop_step_graphs(h));
     h->ent_bound = out_dev_or_null;
     h->ent_kz = kz;
     h->ent_kp = kp;
@@ -968,8 +962,7 @@ extern "C" int zs_gen_actions(zs_handle* h, uint64_t step, int32_t n_discrete, i
     if (!h || !actions_dev) return fail(ZS_EINVAL, "null argument");
     NOT_ON_VIEWER(h, "zs_gen_actions");
     if (n_discrete < 1 || n_discrete > 7) return fail(ZS_EINVAL, "n_discrete must be in 1..7");
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHK(hipSetDevice(h->device));
+    ENTER(h, stream, s);
     HIPCHK(launch_gen_actions(s, h->d, step, n_discrete, actions_dev));
     return ZS_OK;
 }
@@ -993,8 +986,7 @@ extern "C" int zs_step_graph_n(zs_handle* h, uint64_t step0, int32_t n_discrete,
     // n_discrete = 0: the caller's actions (no policy launch; the graph replays zs_step on actions_dev)
     if (n_discrete < 0 || n_discrete > 7) return fail(ZS_EINVAL, "n_discrete must be in 0..7");
     if (n_steps < 1 || n_steps > 64) return fail(ZS_EINVAL, "n_steps must be in 1..64");
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHK(hipSetDevice(h->device));
+    ENTER(h, stream, s);
     const void* key[9] = {actions_dev, obs_dev, rewards_dev, done_dev, trunc_dev, listed_dev, reset_dev,
                           (const void*)(intptr_t)n_discrete, (const void*)(intptr_t)n_steps};
     zs_handle::GraphSet* set = nullptr;
@@ -1009,8 +1001,7 @@ extern "C" int zs_step_graph_n(zs_handle* h, uint64_t step0, int32_t n_discrete,
             if (gs.used < set->used) set = &gs;
         HIPCHK(destroy_graphs(*set));
         if (!h->d_gstep) {
-            int rc = dalloc(h, &h->d_gstep, 2);
-            if (rc) return rc;
+            TRY(dalloc(h, &h->d_gstep, 2));
         }
         uint64_t init[2] = {step0, 0};
         HIPCHK(hipMemcpyAsync(h->d_gstep, init, sizeof(init), hipMemcpyHostToDevice, s));
@@ -1067,8 +1058,7 @@ extern "C" int zs_state_size(const zs_handle* h, int32_t* n_words) {
 extern "C" int zs_get_state(zs_handle* h, int32_t env, int32_t* buf_host, void* stream) {
     if (!h || !buf_host) return fail(ZS_EINVAL, "null argument");
     if (env < 0 || env >= h->d.N) return fail(ZS_EINVAL, "env index out of range");
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHK(hipSetDevice(h->device));
+    ENTER(h, stream, s);
     HIPCHK(launch_get_state(s, h->d, env, h->d_state));
     HIPCHK(hipMemcpyAsync(buf_host, h->d_state, sizeof(int32_t) * h->state_words, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
@@ -1090,22 +1080,19 @@ extern "C" int zs_set_state(zs_handle* h, int32_t env, const int32_t* buf_host, 
         for (int o = 0; o < h->d.O; o++)
             if (hp[o] < ZS_HP_FLOOR) return fail(ZS_EINVAL, "obstacle life below -2147483647");
     }
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHK(hipSetDevice(h->device));
+    ENTER(h, stream, s);
     HIPCHK(hipMemsetAsync(h->d_err, 0, sizeof(int), s));
     HIPCHK(hipMemcpyAsync(h->d_state, buf_host, sizeof(int32_t) * h->state_words, hipMemcpyHostToDevice, s));
     HIPCHK(launch_set_state(s, h->d, env, h->d_state, h->d_err));
     int err;
-    const int rc = read_error_word(h, s, &err);
-    if (rc) return rc;
+    TRY(read_error_word(h, s, &err));
     if (err) return fail(ZS_EINVAL, "state record's needs_reset [5] differs from the engine's (pending resets are not settable)");
     return ZS_OK;
 }
 
 extern "C" int zs_overflow(zs_handle* h, uint32_t* flags_host, int32_t clear, void* stream) {
     if (!h || !flags_host) return fail(ZS_EINVAL, "null argument");
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHK(hipSetDevice(h->device));
+    ENTER(h, stream, s);
     uint32_t f = 0;
     HIPCHK(hipMemcpyAsync(&f, h->d.ovf, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     if (clear) HIPCHK(hipMemsetAsync(h->d.ovf, 0, sizeof(uint32_t), s));
@@ -1133,9 +1120,8 @@ extern "C" int zs_obs_state_layout(const zs_handle* h, int32_t out[12]) {
 
 extern "C" int zs_obs_state_pack(zs_handle* h, void* rec_dev, void* stream) {
     if (!h || !rec_dev) return fail(ZS_EINVAL, "null argument");
-    if ((uintptr_t)rec_dev & 15) return fail(ZS_EINVAL, "rec_dev must be 16-byte aligned");
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHK(hipSetDevice(h->device));
+    TRY(rec_aligned(rec_dev));
+    ENTER(h, stream, s);
     HIPCHK(launch_obs_state_pack(s, h->d, handle_obs_state_layout(h), rec_dev));
     return ZS_OK;
 }
@@ -1147,10 +1133,9 @@ extern "C" int zs_obs_state_unpack(zs_handle* h, const void* rec_dev, int32_t re
     const ObsStateLayout L = handle_obs_state_layout(h);
     if (rec_bytes != L.rec_bytes) return fail(ZS_EINVAL, "rec_bytes differs from the handle's (zs_obs_state_layout)");
     if (env0 < 0 || n < 0 || (int64_t)env0 + n > h->d.N) return fail(ZS_EINVAL, "env range out of bounds");
-    if ((uintptr_t)rec_dev & 15) return fail(ZS_EINVAL, "rec_dev must be 16-byte aligned");
+    TRY(rec_aligned(rec_dev));
     if (n == 0) return ZS_OK;
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHK(hipSetDevice(h->device));
+    ENTER(h, stream, s);
     HIPCHK(launch_obs_state_unpack(s, h->d, L, env0, n, rec_dev));
     return ZS_OK;
 }
@@ -1192,10 +1177,9 @@ extern "C" int zs_snapshot_layout(const zs_handle* h, int32_t out[24]) {
 extern "C" int zs_snapshot(zs_handle* h, const int32_t* env_idx_dev, int32_t n, void* rec_dev, void* stream) {
     if (!h || !rec_dev) return fail(ZS_EINVAL, "null argument");
     if (n < 0) return fail(ZS_EINVAL, "n must be >= 0");
-    if ((uintptr_t)rec_dev & 15) return fail(ZS_EINVAL, "rec_dev must be 16-byte aligned");
+    TRY(rec_aligned(rec_dev));
     if (n == 0) return ZS_OK;
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHK(hipSetDevice(h->device));
+    ENTER(h, stream, s);
     HIPCHK(launch_snapshot(s, snapshot_table(h), h->d.N, env_idx_dev, n, rec_dev));
     return ZS_OK;
 }
@@ -1207,10 +1191,9 @@ extern "C" int zs_restore(zs_handle* h, const void* rec_dev, int32_t rec_bytes, 
     const SnapshotLayout L = handle_snapshot_layout(h);
     if (rec_bytes != L.rec_bytes) return fail(ZS_EINVAL, "rec_bytes differs from the handle's (zs_snapshot_layout)");
     if (n < 0 || n_records < 0) return fail(ZS_EINVAL, "n and n_records must be >= 0");
-    if ((uintptr_t)rec_dev & 15) return fail(ZS_EINVAL, "rec_dev must be 16-byte aligned");
+    TRY(rec_aligned(rec_dev));
     if (n == 0) return ZS_OK;
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHK(hipSetDevice(h->device));
+    ENTER(h, stream, s);
     const Dev& d = h->d;
     // the list the next step drains, rebuilt in place from the restored flags: the copy zeroes its count, the
     // list launch refills it.  rpar stays, the list the next step appends to and the respawn list are empty
@@ -1224,31 +1207,22 @@ extern "C" int zs_restore(zs_handle* h, const void* rec_dev, int32_t rec_bytes, 
 // ---------------------------------------------------------------------------
 // per-env zombie counts and time limits (ZS_FLAG_ENV_PARAMS; k_env_params.hip): asynchronous, nothing read back
 // ---------------------------------------------------------------------------
-static int env_params_refused(const zs_handle* h, const char* call) {
-    if (h->d.flags & ZS_FLAG_ENV_PARAMS) return ZS_OK;
-    return fail(ZS_ESTATE, std::string(call) + ": the handle was created without ZS_FLAG_ENV_PARAMS");
-}
-
 extern "C" int zs_env_params_set(zs_handle* h, const int32_t* env_idx_dev, int32_t n, const int32_t* params_dev, void* stream) {
     if (!h) return fail(ZS_EINVAL, "null handle");
-    int rc = env_params_refused(h, "zs_env_params_set");
-    if (rc) return rc;
+    TRY(need_flag("zs_env_params_set", (h->d.flags & ZS_FLAG_ENV_PARAMS) != 0, "ZS_FLAG_ENV_PARAMS"));
     if (n < 0) return fail(ZS_EINVAL, "n must be >= 0");
     if (n == 0) return ZS_OK;
     if (n > (1 << 30)) return fail(ZS_EINVAL, "n must be <= 2^30");
     if (!params_dev) return fail(ZS_EINVAL, "null argument");
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHK(hipSetDevice(h->device));
+    ENTER(h, stream, s);
     HIPCHK(launch_env_params_set(s, h->d, h->d_envp_owner, env_idx_dev, n, params_dev));
     return ZS_OK;
 }
 
 extern "C" int zs_env_params_check(zs_handle* h, uint32_t* refused_host, void* stream) {
     if (!h || !refused_host) return fail(ZS_EINVAL, "null argument");
-    int rc = env_params_refused(h, "zs_env_params_check");
-    if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHK(hipSetDevice(h->device));
+    TRY(need_flag("zs_env_params_check", (h->d.flags & ZS_FLAG_ENV_PARAMS) != 0, "ZS_FLAG_ENV_PARAMS"));
+    ENTER(h, stream, s);
     uint32_t* word = (uint32_t*)(h->d_envp_owner + h->d.N);
     HIPCHK(launch_env_params_check(s, h->d, word));
     uint32_t f = 0;
@@ -1260,11 +1234,9 @@ extern "C" int zs_env_params_check(zs_handle* h, uint32_t* refused_host, void* s
 
 extern "C" int zs_env_params_get(zs_handle* h, int32_t which, int32_t* out_dev, void* stream) {
     if (!h || !out_dev) return fail(ZS_EINVAL, "null argument");
-    int rc = env_params_refused(h, "zs_env_params_get");
-    if (rc) return rc;
+    TRY(need_flag("zs_env_params_get", (h->d.flags & ZS_FLAG_ENV_PARAMS) != 0, "ZS_FLAG_ENV_PARAMS"));
     if (which != 0 && which != 1) return fail(ZS_EINVAL, "which must be 0 (next) or 1 (current)");
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHK(hipSetDevice(h->device));
+    ENTER(h, stream, s);
     HIPCHK(launch_env_params_get(s, h->d, which, out_dev));
     return ZS_OK;
 }
@@ -1272,15 +1244,9 @@ extern "C" int zs_env_params_get(zs_handle* h, int32_t which, int32_t* out_dev, 
 // ---------------------------------------------------------------------------
 // per-env episode statistics (ZS_FLAG_EPISODE_STATS; k_episode.hip): asynchronous, nothing read back
 // ---------------------------------------------------------------------------
-static int episode_stats_refused(const zs_handle* h, const char* call) {
-    if (h->ep.run) return ZS_OK;
-    return fail(ZS_ESTATE, std::string(call) + ": the handle was created without ZS_FLAG_EPISODE_STATS");
-}
-
 extern "C" int zs_episode_stats_layout(const zs_handle* h, int32_t out[8]) {
     if (!h || !out) return fail(ZS_EINVAL, "null argument");
-    int rc = episode_stats_refused(h, "zs_episode_stats_layout");
-    if (rc) return rc;
+    TRY(need_flag("zs_episode_stats_layout", h->ep.run != nullptr, "ZS_FLAG_EPISODE_STATS"));
     const SnapshotLayout L = handle_snapshot_layout(h);
     const int32_t v[8] = {h->ep.R, ZS_EP_LAST, ZS_EP_TOT, L.ep_run, L.ep_bytes, 0, 0, 0};
     std::memcpy(out, v, sizeof(v));
@@ -1290,20 +1256,16 @@ extern "C" int zs_episode_stats_layout(const zs_handle* h, int32_t out[8]) {
 extern "C" int zs_episode_stats_get(zs_handle* h, const uint8_t* env_mask_dev, double* run_ret_dev, double* last_ret_dev,
                                     double* sum_ret_dev, int32_t* last_dev, uint32_t* tot_dev, void* stream) {
     if (!h) return fail(ZS_EINVAL, "null handle");
-    int rc = episode_stats_refused(h, "zs_episode_stats_get");
-    if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHK(hipSetDevice(h->device));
+    TRY(need_flag("zs_episode_stats_get", h->ep.run != nullptr, "ZS_FLAG_EPISODE_STATS"));
+    ENTER(h, stream, s);
     HIPCHK(launch_episode_get(s, h->ep, env_mask_dev, run_ret_dev, last_ret_dev, sum_ret_dev, last_dev, tot_dev));
     return ZS_OK;
 }
 
 extern "C" int zs_episode_stats_clear(zs_handle* h, const uint8_t* env_mask_dev, void* stream) {
     if (!h) return fail(ZS_EINVAL, "null handle");
-    int rc = episode_stats_refused(h, "zs_episode_stats_clear");
-    if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHK(hipSetDevice(h->device));
+    TRY(need_flag("zs_episode_stats_clear", h->ep.run != nullptr, "ZS_FLAG_EPISODE_STATS"));
+    ENTER(h, stream, s);
     HIPCHK(launch_episode_clear(s, h->ep, env_mask_dev, 0));
     return ZS_OK;
 }
@@ -1311,15 +1273,9 @@ extern "C" int zs_episode_stats_clear(zs_handle* h, const uint8_t* env_mask_dev,
 // ---------------------------------------------------------------------------
 // the envs' picture (ZS_FLAG_RENDER; k_render.hip, zs_render.hpp)
 // ---------------------------------------------------------------------------
-static int render_refused(const zs_handle* h, const char* call) {
-    if (h->rn.body_col) return ZS_OK;
-    return fail(ZS_ESTATE, std::string(call) + ": the handle was created without ZS_FLAG_RENDER");
-}
-
 extern "C" int zs_render_layout(const zs_handle* h, int32_t out[8]) {
     if (!h || !out) return fail(ZS_EINVAL, "null argument");
-    int rc = render_refused(h, "zs_render_layout");
-    if (rc) return rc;
+    TRY(need_flag("zs_render_layout", h->rn.body_col != nullptr, "ZS_FLAG_RENDER"));
     const RenderPlan& p = h->rn.plan;
     const int32_t v[8] = {p.frame_h, p.frame_w, p.frame_bytes, ZS_RENDER_CELL, ZS_RENDER_MASK, ZS_RENDER_PALETTE, p.body_bytes,
                           handle_snapshot_layout(h).body_col};
@@ -1329,24 +1285,20 @@ extern "C" int zs_render_layout(const zs_handle* h, int32_t out[8]) {
 
 extern "C" int zs_render(zs_handle* h, const int32_t* envs_dev, int32_t n, uint8_t* out_dev, int32_t n_frames, void* stream) {
     if (!h) return fail(ZS_EINVAL, "null handle");
-    int rc = render_refused(h, "zs_render");
-    if (rc) return rc;
+    TRY(need_flag("zs_render", h->rn.body_col != nullptr, "ZS_FLAG_RENDER"));
     if (n < 0 || n_frames < 0) return fail(ZS_EINVAL, "zs_render: negative count");
     const long frames = std::min(n, n_frames);
     if (frames == 0) return ZS_OK;
     if (!out_dev) return fail(ZS_EINVAL, "zs_render: null output");
     if (frames * h->rn.plan.bands > 0x7fffffffL) return fail(ZS_EINVAL, "zs_render: too many frames for one launch");
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHK(hipSetDevice(h->device));
-    const hipError_t e = launch_render(s, h->rn, envs_dev, n, out_dev, n_frames);
-    if (e != hipSuccess) return fail(ZS_EHIP, std::string("k_render: ") + hipGetErrorString(e));
+    ENTER(h, stream, s);
+    LAUNCHCHK("k_render", launch_render(s, h->rn, envs_dev, n, out_dev, n_frames));
     return ZS_OK;
 }
 
 extern "C" int zs_render_sprites(zs_handle* h, const uint32_t masks[5][4], const uint8_t palette[8][3]) {
     if (!h || !masks || !palette) return fail(ZS_EINVAL, "null argument");
-    int rc = render_refused(h, "zs_render_sprites");
-    if (rc) return rc;
+    TRY(need_flag("zs_render_sprites", h->rn.body_col != nullptr, "ZS_FLAG_RENDER"));
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipDeviceSynchronize());  // the atlas is a launch argument: frames already queued keep the one they took
     RenderAtlas& a = h->rn.atlas;
@@ -1367,8 +1319,7 @@ extern "C" int zs_render_sprites(zs_handle* h, const uint32_t masks[5][4], const
 extern "C" int zs_get_rng(zs_handle* h, int32_t env, uint32_t* state_host, void* stream) {
     if (!h || !state_host) return fail(ZS_EINVAL, "null argument");
     if (env < 0 || env >= h->d.N) return fail(ZS_EINVAL, "env index out of range");
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHK(hipSetDevice(h->device));
+    ENTER(h, stream, s);
     uint32_t st = 0;
     std::vector<uint32_t> ring(ZS_RING_WORDS);
     HIPCHK(hipMemcpyAsync(&st, h->d.rngst + env, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
@@ -1398,8 +1349,7 @@ extern "C" int zs_set_rng(zs_handle* h, int32_t env, const uint32_t* state_host,
     NOT_ON_VIEWER(h, "zs_set_rng");
     if (env < 0 || env >= h->d.N) return fail(ZS_EINVAL, "env index out of range");
     if (state_host[ZS_MT_N] > ZS_MT_N) return fail(ZS_EINVAL, "MT index out of range (0..624)");
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHK(hipSetDevice(h->device));
+    ENTER(h, stream, s);
     std::vector<uint32_t> ring(ZS_RING_WORDS);
     const uint32_t st = ring_from_state(ring.data(), state_host);
     HIPCHK(hipMemcpyAsync(h->d.ring + (size_t)env * ZS_RING_WORDS, ring.data(), sizeof(uint32_t) * ZS_RING_WORDS,
@@ -1466,8 +1416,7 @@ static int read_log(zs_handle* h, const int32_t* log, const int32_t* log_n, int 
     if (!h || !n_out || (cap > 0 && !out_host)) return fail(ZS_EINVAL, "null argument");
     if (!log) return fail(ZS_EINVAL, "the handle was created without ZS_FLAG_DEATH_LOG");
     if (env < 0 || env >= h->d.N) return fail(ZS_EINVAL, "env out of range");
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHK(hipSetDevice(h->device));
+    ENTER(h, stream, s);
     int32_t n = 0;
     HIPCHK(hipMemcpyAsync(&n, log_n + env, sizeof(int32_t), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
@@ -1528,10 +1477,9 @@ static int host_init(zs_handle* h) {
     const size_t N = d.N;
     HostLayout L = host_layout(h);
     const size_t in_words = N * d.A * 3 + N * (ZS_RING_WORDS + 1);
-    int rc;
-    if ((rc = dalloc(h, &h->d_hobs, N * L.obs_bytes)) || (rc = dalloc(h, &h->d_hrew, N * L.R)) ||
-        (rc = dalloc(h, &h->d_hflags, N * (3 + d.A))))
-        return rc;
+    TRY(dalloc(h, &h->d_hobs, N * L.obs_bytes));
+    TRY(dalloc(h, &h->d_hrew, N * L.R));
+    TRY(dalloc(h, &h->d_hflags, N * (3 + d.A)));
     // coherent (uncached on the device) so the kernels see this call's input and the host the record
     // without copies; the blocks are a few KB per env
     const unsigned fl = hipHostMallocMapped | hipHostMallocCoherent;
@@ -1626,8 +1574,7 @@ extern "C" int zs_host_observe(zs_handle* h, int32_t* rec_host, void* stream) {
 // step drains).
 extern "C" int zs_debug_lists(zs_handle* h, int32_t* out, void* stream) {
     if (!h || !out) return fail(ZS_EINVAL, "null argument");
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHK(hipSetDevice(h->device));
+    ENTER(h, stream, s);
     int v[3] = {0, 0, 0};
     HIPCHK(hipMemcpyAsync(v, h->d_rcount, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(v + 2, h->d.resp_count, sizeof(int), hipMemcpyDeviceToHost, s));

@@ -12,17 +12,7 @@ import numpy as np
 from . import _abi
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_build", "libzombsole_mi355x.so")
-SYMBOLS = ["zs_last_error", "zs_create", "zs_destroy", "zs_obs_shape", "zs_seed", "zs_reset", "zs_step", "zs_observe",
-           "zs_gen_actions", "zs_step_graph", "zs_step_graph_n", "zs_state_size", "zs_get_state", "zs_set_state", "zs_get_rng", "zs_set_rng", "zs_overflow", "zs_profile", "zs_profile_read", "zs_describe",
-           "zs_debug_stamps", "zs_debug_stamps_wg", "zs_debug_timeline", "zs_debug_lists", "zs_death_log", "zs_action_log",
-           "zs_host_layout", "zs_host_step", "zs_host_reset", "zs_host_observe",
-           "zs_obs_state_layout", "zs_obs_state_pack", "zs_obs_state_unpack",
-           "zs_snapshot_layout", "zs_snapshot", "zs_restore",
-           "zs_action_mask", "zs_action_mask_bind",
-           "zs_entity_obs_layout", "zs_entity_obs", "zs_entity_obs_bind",
-           "zs_env_params_set", "zs_env_params_get", "zs_env_params_check",
-           "zs_episode_stats_layout", "zs_episode_stats_get", "zs_episode_stats_clear",
-           "zs_render_layout", "zs_render", "zs_render_sprites"]
+SYMBOLS = list(_abi.ABI)
 
 _lib = None
 
@@ -46,60 +36,10 @@ def load_library(path=None):
     # /opt/rocm into the process, which cannot open the device once torch's runtime owns it.
     import torch  # noqa: F401
     L = C.CDLL(p)
-    vp, i32, u64 = C.c_void_p, C.c_int32, C.c_uint64
-    L.zs_last_error.restype = C.c_char_p
-    L.zs_create.argtypes = [vp, C.c_int, C.POINTER(vp)]
-    L.zs_destroy.argtypes = [vp]
-    L.zs_obs_shape.argtypes = [vp, C.POINTER(i32)]
-    L.zs_seed.argtypes = [vp, i32, i32, C.POINTER(u64), vp]
-    L.zs_reset.argtypes = [vp, vp, vp, vp]
-    L.zs_step.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.zs_observe.argtypes = [vp, vp, vp, vp]
-    L.zs_gen_actions.argtypes = [vp, u64, i32, vp, vp]
-    L.zs_step_graph.argtypes = [vp, u64, i32, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.zs_step_graph_n.argtypes = [vp, u64, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.zs_state_size.argtypes = [vp, C.POINTER(i32)]
-    L.zs_get_state.argtypes = [vp, i32, vp, vp]
-    L.zs_set_state.argtypes = [vp, i32, vp, vp]
-    L.zs_get_rng.argtypes = [vp, i32, vp, vp]
-    L.zs_set_rng.argtypes = [vp, i32, vp, vp]
-    L.zs_overflow.argtypes = [vp, C.POINTER(C.c_uint32), i32, vp]
-    L.zs_profile.argtypes = [vp, i32]
-    L.zs_profile_read.argtypes = [vp, C.POINTER(C.c_double)]
-    L.zs_debug_stamps.argtypes = [vp, vp, vp, i32]
-    L.zs_describe.argtypes = [vp, C.c_char_p, i32]
-    L.zs_debug_lists.argtypes = [vp, C.POINTER(i32), vp]
-    L.zs_death_log.argtypes = [vp, i32, C.POINTER(i32), i32, C.POINTER(i32), vp]
-    L.zs_action_log.argtypes = [vp, i32, C.POINTER(i32), i32, C.POINTER(i32), vp]
-    L.zs_debug_timeline.argtypes = [vp, vp, i32]
-    L.zs_debug_stamps_wg.argtypes = [vp, vp, i32, i32]
-    L.zs_host_layout.argtypes = [vp, C.POINTER(i32)]
-    L.zs_host_step.argtypes = [vp, vp, vp, vp, vp]
-    L.zs_host_reset.argtypes = [vp, vp, vp, vp]
-    L.zs_host_observe.argtypes = [vp, vp, vp]
-    L.zs_obs_state_layout.argtypes = [vp, C.POINTER(i32)]
-    L.zs_obs_state_pack.argtypes = [vp, vp, vp]
-    L.zs_obs_state_unpack.argtypes = [vp, vp, i32, i32, i32, vp]
-    L.zs_snapshot_layout.argtypes = [vp, C.POINTER(i32)]
-    L.zs_snapshot.argtypes = [vp, vp, i32, vp, vp]
-    L.zs_restore.argtypes = [vp, vp, i32, i32, vp, vp, i32, vp]
-    L.zs_action_mask.argtypes = [vp, vp, vp, vp]
-    L.zs_action_mask_bind.argtypes = [vp, vp]
-    L.zs_entity_obs_layout.argtypes = [vp, i32, i32, C.POINTER(i32)]
-    L.zs_entity_obs.argtypes = [vp, vp, i32, i32, vp, vp]
-    L.zs_entity_obs_bind.argtypes = [vp, vp, i32, i32]
-    L.zs_env_params_set.argtypes = [vp, vp, i32, vp, vp]
-    L.zs_env_params_get.argtypes = [vp, i32, vp, vp]
-    L.zs_env_params_check.argtypes = [vp, C.POINTER(C.c_uint32), vp]
-    L.zs_episode_stats_layout.argtypes = [vp, C.POINTER(i32)]
-    L.zs_episode_stats_get.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
-    L.zs_episode_stats_clear.argtypes = [vp, vp, vp]
-    L.zs_render_layout.argtypes = [vp, C.POINTER(i32)]
-    L.zs_render.argtypes = [vp, vp, i32, vp, i32, vp]
-    L.zs_render_sprites.argtypes = [vp, vp, vp]
-    for s in SYMBOLS:
-        if s != "zs_last_error":
-            getattr(L, s).restype = C.c_int
+    for name, argtypes in _abi.ABI.items():
+        f = getattr(L, name)
+        f.argtypes = argtypes
+        f.restype = C.c_char_p if name == "zs_last_error" else C.c_int
     if path is None:
         _lib = L
     return L
@@ -137,6 +77,42 @@ def _np_ptr(a):
     return C.c_void_p(a.ctypes.data)
 
 
+def _to_int32(torch, x, device):
+    """An integer tensor as a contiguous int32 tensor on `device`; a value int32 does not hold becomes -1 (no env, no
+    record, no count and no limit is -1: the device refuses or skips the entry) instead of wrapping into range.  No
+    synchronisation."""
+    x = x.to(device)
+    if x.dtype != torch.int32:
+        x = x.to(torch.int64)
+        x = torch.where((x < -2 ** 31) | (x > 2 ** 31 - 1), torch.full_like(x, -1), x)
+    return x.to(torch.int32).contiguous()
+
+
+def as_index(torch, x, device, what):
+    """`x` (a sequence or tensor of env / record numbers) as a contiguous int32 1-D tensor on `device`, by _to_int32's
+    rule; ValueError for bool, float or other than 1-D input.  None (the call's default order) stays None."""
+    if x is None:
+        return None
+    if not torch.is_tensor(x):
+        x = torch.as_tensor(x)
+        if x.numel() == 0:  # an empty sequence has no integer dtype of its own
+            x = x.to(torch.int32)
+    if x.dim() != 1 or x.dtype == torch.bool or x.is_floating_point() or x.is_complex():
+        raise ValueError("%s: an index is a 1-D integer tensor or sequence" % what)
+    return _to_int32(torch, x, device)
+
+
+def check_tensor(t, what, dtype, device, rows, trailing, at_least=False, align=0):
+    """ValueError unless `t` is a contiguous `dtype` tensor [rows, *trailing] on `device` (at_least: `rows` or more
+    leading rows) at an address that is a multiple of `align` (0: any).  `what` names the call and the tensor."""
+    shape = tuple(t.shape)
+    if (t.dtype != dtype or t.device != device or not t.is_contiguous() or shape[1:] != tuple(trailing) or not shape or
+            (shape[0] < rows if at_least else shape[0] != rows) or (align and t.data_ptr() % align)):
+        raise ValueError("%s must be a contiguous%s %s tensor [%s%d%s] on %s"
+                         % (what, ", %d-byte aligned" % align if align else "", dtype, "rows >= " if at_least else "",
+                            rows, "".join(", %d" % w for w in trailing), device))
+
+
 def decode_action_log(words, n, E):
     """(actions, raised) from zs_action_log's words and count (n < 0: a debug raise, -1 - n entries)."""
     raised = n < 0
@@ -170,11 +146,12 @@ class Engine(object):
         # that runtime without a device context (hipSetDevice then reports no device).
         torch.zeros(1, device=self.device)
         self.h = C.c_void_p()
+        self._layouts = {}  # _layout's cache: (call, arguments) -> dict
         rc = self.L.zs_create(C.cast(builder.ptr(), C.c_void_p), self.device.index, C.byref(self.h))
         if rc:
             _raise(self.L, rc, "zs_create")
         shp = (C.c_int32 * 4)()
-        self.L.zs_obs_shape(self.h, shp)
+        self._call("zs_obs_shape", shp)
         self.obs_shape = tuple(int(v) for v in shp)
         self.N = builder.cfg.num_envs
         self.A = builder.num_agents
@@ -190,7 +167,7 @@ class Engine(object):
         self.listed, self.was_reset = self.out.listed, self.out.was_reset
         self.actions = torch.zeros((self.N, self.A, 3), dtype=torch.int32, **kw)
         n = C.c_int32()
-        self.L.zs_state_size(self.h, C.byref(n))
+        self._call("zs_state_size", C.byref(n))
         self.state_words = int(n.value)
         self.n_discrete = 7 if self.multi else 6
         self.masks = None  # the bound action-mask tensor (bind_action_masks), uint8 [N, A, 8]
@@ -211,17 +188,29 @@ class Engine(object):
     def _stream(self):
         return C.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
 
+    def _call(self, name, *args):
+        """The C ABI's `name` on this handle; a nonzero status is raised (_raise) under the call's name."""
+        rc = getattr(self.L, name)(self.h, *args)
+        if rc:
+            _raise(self.L, rc, name)
+
+    def _layout(self, name, *args):
+        """The layout call `name` as a dict of its _abi.LAYOUT_KEYS (reserved words left out), read once per
+        argument set."""
+        if (name,) + args not in self._layouts:
+            keys = _abi.LAYOUT_KEYS[name]
+            out = (C.c_int32 * len(keys))()
+            self._call(name, *args + (out,))
+            self._layouts[(name,) + args] = {k: int(v) for k, v in zip(keys, out) if k is not None}
+        return self._layouts[(name,) + args]
+
     def seed(self, seeds, env0=0):
         arr = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64).reshape(-1))
-        rc = self.L.zs_seed(self.h, env0, len(arr), arr.ctypes.data_as(C.POINTER(C.c_uint64)), self._stream())
-        if rc:
-            _raise(self.L, rc, "zs_seed")
+        self._call("zs_seed", env0, len(arr), arr.ctypes.data_as(C.POINTER(C.c_uint64)), self._stream())
 
     def reset(self, mask=None):
         """Reset envs (all, or where the uint8 device tensor `mask` is nonzero)."""
-        rc = self.L.zs_reset(self.h, _ptr(mask), _ptr(self.obs), self._stream())
-        if rc:
-            _raise(self.L, rc, "zs_reset")
+        self._call("zs_reset", _ptr(mask), _ptr(self.obs), self._stream())
         return self.obs
 
     def outputs(self, rows=None, obs=None, flat=None):
@@ -235,10 +224,8 @@ class Engine(object):
         outputs into `out` (default: self.out)."""
         a = self.actions if actions is None else actions
         o = self.out if out is None else out
-        rc = self.L.zs_step(self.h, _ptr(a), _ptr(o.obs), _ptr(o.rewards), _ptr(o.done),
-                            _ptr(o.trunc), _ptr(o.listed), _ptr(o.was_reset), self._stream())
-        if rc:
-            _raise(self.L, rc, "zs_step")
+        self._call("zs_step", _ptr(a), _ptr(o.obs), _ptr(o.rewards), _ptr(o.done), _ptr(o.trunc), _ptr(o.listed),
+                   _ptr(o.was_reset), self._stream())
         return self._obs_rows(o), o.rewards[:self.N], o.done[:self.N], o.trunc[:self.N]
 
     def _obs_rows(self, o):
@@ -252,16 +239,12 @@ class Engine(object):
         fills on the current stream before each call (see step_graphed)."""
         o = self.out if out is None else out
         a = self.actions if actions is None else actions
+        bufs = (_ptr(a), _ptr(o.obs), _ptr(o.rewards), _ptr(o.done), _ptr(o.trunc), _ptr(o.listed), _ptr(o.was_reset),
+                self._stream())
         if steps == 1:
-            rc = self.L.zs_step_graph(self.h, int(step0), int(n_discrete), _ptr(a), _ptr(o.obs),
-                                      _ptr(o.rewards), _ptr(o.done), _ptr(o.trunc), _ptr(o.listed),
-                                      _ptr(o.was_reset), self._stream())
+            self._call("zs_step_graph", int(step0), int(n_discrete), *bufs)
         else:
-            rc = self.L.zs_step_graph_n(self.h, int(step0), int(n_discrete), int(steps), _ptr(a),
-                                        _ptr(o.obs), _ptr(o.rewards), _ptr(o.done), _ptr(o.trunc), _ptr(o.listed),
-                                        _ptr(o.was_reset), self._stream())
-        if rc:
-            _raise(self.L, rc, "zs_step_graph")
+            self._call("zs_step_graph_n", int(step0), int(n_discrete), int(steps), *bufs)
         return self._obs_rows(o), o.rewards[:self.N], o.done[:self.N], o.trunc[:self.N]
 
     def step_graphed(self, actions=None, out=None):
@@ -279,23 +262,11 @@ class Engine(object):
         if o is None:
             raise ValueError("observe: this engine keeps no grid observations (grid_obs=False); pass out=")
         if out is not None:
-            if (o.dtype != self.obs_dtype or o.device != self.device or not o.is_contiguous() or
-                    tuple(o.shape[1:]) != tuple(self.obs_shape) or o.shape[0] < self.N):
-                raise ValueError("observe: out must be a contiguous %s tensor [rows >= %d]%s on %s"
-                                 % (self.obs_dtype, self.N, list(self.obs_shape), self.device))
-        rc = self.L.zs_observe(self.h, _ptr(mask), _ptr(o), self._stream())
-        if rc:
-            _raise(self.L, rc, "zs_observe")
+            check_tensor(o, "observe: out", self.obs_dtype, self.device, self.N, self.obs_shape, at_least=True)
+        self._call("zs_observe", _ptr(mask), _ptr(o), self._stream())
         return o
 
     # -- action masks of the discrete tables (zs_action_mask*) ------------------------------------------------------
-    def _check_masks(self, m, what):
-        t = self.torch
-        if (m.dtype != t.uint8 or m.device != self.device or not m.is_contiguous() or m.data_ptr() % 8 or
-                tuple(m.shape) != (self.N, self.A, 8)):
-            raise ValueError("%s: masks are a contiguous, 8-byte aligned uint8 tensor [%d, %d, 8] on %s"
-                             % (what, self.N, self.A, self.device))
-
     def action_mask(self, mask=None, out=None):
         """The action masks of the current state, uint8 [N, A, 8] (zs_action_mask): entry k of agent a is 1 when
         the reference would carry out discrete action k for it; entries at k >= n_discrete are 0, absent agents
@@ -304,10 +275,8 @@ class Engine(object):
         o = out if out is not None else self.masks
         if o is None:
             o = self.torch.zeros((self.N, self.A, 8), dtype=self.torch.uint8, device=self.device)
-        self._check_masks(o, "action_mask")
-        rc = self.L.zs_action_mask(self.h, _ptr(mask), _ptr(o), self._stream())
-        if rc:
-            _raise(self.L, rc, "zs_action_mask")
+        check_tensor(o, "action_mask: masks", self.torch.uint8, self.device, self.N, (self.A, 8), align=8)
+        self._call("zs_action_mask", _ptr(mask), _ptr(o), self._stream())
         return o
 
     def bind_action_masks(self, buf=True):
@@ -318,10 +287,8 @@ class Engine(object):
         elif buf is False:
             buf = None
         if buf is not None:
-            self._check_masks(buf, "bind_action_masks")
-        rc = self.L.zs_action_mask_bind(self.h, _ptr(buf))
-        if rc:
-            _raise(self.L, rc, "zs_action_mask_bind")
+            check_tensor(buf, "bind_action_masks: masks", self.torch.uint8, self.device, self.N, (self.A, 8), align=8)
+        self._call("zs_action_mask_bind", _ptr(buf))
         self.masks = buf
         return buf
 
@@ -331,13 +298,7 @@ class Engine(object):
         """zs_entity_obs_layout as a dict: "row_words", the word offsets "self", "zombies", "players", "objective",
         "rays", "ray_cap" and "row_bytes", with "kz" and "kp" (default: the bound tensor's)."""
         kz, kp = self._entity_k(kz, kp)
-        out = (C.c_int32 * 8)()
-        rc = self.L.zs_entity_obs_layout(self.h, kz, kp, out)
-        if rc:
-            _raise(self.L, rc, "zs_entity_obs_layout")
-        L = dict(zip(_abi.ENTITY_LAYOUT_KEYS, (int(v) for v in out)))
-        L.update(kz=kz, kp=kp)
-        return L
+        return dict(self._layout("zs_entity_obs_layout", kz, kp), kz=kz, kp=kp)
 
     def _entity_k(self, kz, kp):
         if kz is None and kp is None and self.entity_k is not None:
@@ -347,11 +308,8 @@ class Engine(object):
         return int(kz), int(kp)
 
     def _check_entities(self, t, kz, kp, what):
-        L = _abi.entity_layout(kz, kp)  # ValueError on bad K values
-        if (t.dtype != self.torch.int16 or t.device != self.device or not t.is_contiguous() or t.data_ptr() % 8 or
-                tuple(t.shape) != (self.N, self.A, L["row_words"])):
-            raise ValueError("%s: entity observations are a contiguous, 8-byte aligned int16 tensor [%d, %d, %d] on %s"
-                             % (what, self.N, self.A, L["row_words"], self.device))
+        row = _abi.entity_layout(kz, kp)["row_words"]  # ValueError on bad K values
+        check_tensor(t, what + ": entity observations", self.torch.int16, self.device, self.N, (self.A, row), align=8)
 
     def entity_obs(self, mask=None, out=None, kz=None, kp=None):
         """The entity observations of the current state, int16 [N, A, 16 + 4 (kz + kp)] (zs_entity_obs; the layout:
@@ -366,9 +324,7 @@ class Engine(object):
             o = self.torch.zeros((self.N, self.A, _abi.entity_layout(kz, kp)["row_words"]), dtype=self.torch.int16,
                                  device=self.device)
         self._check_entities(o, kz, kp, "entity_obs")
-        rc = self.L.zs_entity_obs(self.h, _ptr(mask), kz, kp, _ptr(o), self._stream())
-        if rc:
-            _raise(self.L, rc, "zs_entity_obs")
+        self._call("zs_entity_obs", _ptr(mask), kz, kp, _ptr(o), self._stream())
         return o
 
     def bind_entity_obs(self, buf=True, kz=4, kp=1):
@@ -382,9 +338,7 @@ class Engine(object):
             buf = None
         if buf is not None:
             self._check_entities(buf, kz, kp, "bind_entity_obs")
-        rc = self.L.zs_entity_obs_bind(self.h, _ptr(buf), int(kz) if buf is not None else 0, int(kp) if buf is not None else 0)
-        if rc:
-            _raise(self.L, rc, "zs_entity_obs_bind")
+        self._call("zs_entity_obs_bind", _ptr(buf), int(kz) if buf is not None else 0, int(kp) if buf is not None else 0)
         self.entities = buf
         self.entity_k = (int(kz), int(kp)) if buf is not None else None
         return buf
@@ -393,22 +347,12 @@ class Engine(object):
     def obs_state_layout(self):
         """zs_obs_state_layout as a dict: the byte offset of every section of an env's record (the names of
         _abi.OBS_STATE_SECTIONS), "pad", "rec_bytes" and "hp_bytes"."""
-        if getattr(self, "_osl", None) is None:
-            out = (C.c_int32 * 12)()
-            rc = self.L.zs_obs_state_layout(self.h, out)
-            if rc:
-                _raise(self.L, rc, "zs_obs_state_layout")
-            names = ("rec_bytes",) + _abi.OBS_STATE_SECTIONS + ("pad", "hp_bytes")
-            self._osl = dict(zip(names, [int(v) for v in out]))
-        return self._osl
+        return self._layout("zs_obs_state_layout")
 
-    def _check_records(self, rec, what, rows):
-        t = self.torch
-        nb = self.obs_state_layout()["rec_bytes"]
-        if (rec.dtype != t.uint8 or rec.dim() != 2 or rec.shape[1] != nb or not rec.is_contiguous() or
-                rec.device != self.device or rec.shape[0] < rows or rec.data_ptr() % 16):
-            raise ValueError("%s: records are a contiguous, 16-byte aligned uint8 tensor [rows >= %d, %d] on %s"
-                             % (what, rows, nb, self.device))
+    def _check_records(self, rec, what, rows, layout):
+        """`rec` holds at least `rows` records of `layout` (obs_state_layout() or snapshot_layout())."""
+        check_tensor(rec, what + ": records", self.torch.uint8, self.device, rows, (layout["rec_bytes"],), at_least=True,
+                     align=16)
 
     def pack_obs_state(self, out=None):
         """Every env's observation-state record into `out`, uint8 [rows >= N, rec_bytes] (default: a new
@@ -416,68 +360,40 @@ class Engine(object):
         if out is None:
             out = self.torch.empty((self.N, self.obs_state_layout()["rec_bytes"]), dtype=self.torch.uint8,
                                    device=self.device)
-        self._check_records(out, "pack_obs_state", self.N)
-        rc = self.L.zs_obs_state_pack(self.h, _ptr(out), self._stream())
-        if rc:
-            _raise(self.L, rc, "zs_obs_state_pack")
+        self._check_records(out, "pack_obs_state", self.N, self.obs_state_layout())
+        self._call("zs_obs_state_pack", _ptr(out), self._stream())
         return out
 
     def unpack_obs_state(self, rec, env0=0, n=None):
         """Viewer engines only: records rec[:n] (default: all rows) into envs [env0, env0 + n); observe() then
         encodes them.  The records come from engines of the same map, entity counts and observation form."""
         n = rec.shape[0] if n is None else int(n)
-        self._check_records(rec, "unpack_obs_state", n)
-        rc = self.L.zs_obs_state_unpack(self.h, _ptr(rec), int(rec.shape[1]), int(env0), n, self._stream())
-        if rc:
-            _raise(self.L, rc, "zs_obs_state_unpack")
+        self._check_records(rec, "unpack_obs_state", n, self.obs_state_layout())
+        self._call("zs_obs_state_unpack", _ptr(rec), int(rec.shape[1]), int(env0), n, self._stream())
 
     # -- snapshot records (zs_snapshot / zs_restore): complete envs, for checkpoints, rewinds and forks -------------
     def snapshot_layout(self):
         """zs_snapshot_layout as a dict: the byte offset of every section of an env's snapshot record (the names
         of _abi.SNAPSHOT_SECTIONS), "pad", "rec_bytes" and "fingerprint" (handles whose fingerprints agree can
         exchange records)."""
-        if getattr(self, "_snl", None) is None:
-            out = (C.c_int32 * 24)()
-            rc = self.L.zs_snapshot_layout(self.h, out)
-            if rc:
-                _raise(self.L, rc, "zs_snapshot_layout")
-            v = [int(x) for x in out]
-            L = dict(zip(("rec_bytes",) + _abi.SNAPSHOT_SECTIONS + ("pad",), v))
-            L["fingerprint"] = (v[19] & 0xffffffff) | ((v[20] & 0xffffffff) << 32)
-            if v[23]:  # a FLAG_ENV_PARAMS handle's record: the current triple, then the next one
-                L["env_params"] = v[23]
-            self._snl = L
-        return self._snl
-
-    def _index(self, idx, what):
-        """None, or `idx` (a sequence or tensor of env / record numbers) as a contiguous int32 device tensor."""
-        t = self.torch
-        if idx is None:
-            return None
-        idx = t.as_tensor(idx)
-        if idx.dim() != 1 or idx.dtype in (t.bool, t.float16, t.float32, t.float64):
-            raise ValueError("%s: an index is a 1-D integer tensor or sequence" % what)
-        return idx.to(device=self.device, dtype=t.int32).contiguous()
-
-    def _check_snapshot(self, rec, what, rows=0):
-        t = self.torch
-        nb = self.snapshot_layout()["rec_bytes"]
-        if (rec.dtype != t.uint8 or rec.dim() != 2 or rec.shape[1] != nb or not rec.is_contiguous() or
-                rec.device != self.device or rec.shape[0] < rows or rec.data_ptr() % 16):
-            raise ValueError("%s: records are a contiguous, 16-byte aligned uint8 tensor [rows >= %d, %d] on %s"
-                             % (what, rows, nb, self.device))
+        L = dict(self._layout("zs_snapshot_layout"))
+        lo, hi = L.pop("fingerprint_lo"), L.pop("fingerprint_hi")
+        L["fingerprint"] = (lo & 0xffffffff) | ((hi & 0xffffffff) << 32)
+        del L["nscal"], L["ring_words"]  # the record format's constants (_abi.SNAPSHOT_NSCAL, SNAPSHOT_RING)
+        if not L["env_params"]:  # nonzero in a FLAG_ENV_PARAMS handle's record: the current triple, then the next one
+            del L["env_params"]
+        return L
 
     def snapshot(self, envs=None, out=None):
         """The snapshot records of `envs` (default: all N, in order; duplicates allowed) as uint8 [n, rec_bytes]
         (into the first n rows of `out` when given).  Asynchronous on the current stream."""
-        idx = self._index(envs, "snapshot")
+        idx = as_index(self.torch, envs, self.device, "snapshot")
         n = self.N if idx is None else int(idx.shape[0])
+        L = self.snapshot_layout()
         if out is None:
-            out = self.torch.empty((n, self.snapshot_layout()["rec_bytes"]), dtype=self.torch.uint8, device=self.device)
-        self._check_snapshot(out, "snapshot", n)
-        rc = self.L.zs_snapshot(self.h, _ptr(idx), n, _ptr(out), self._stream())
-        if rc:
-            _raise(self.L, rc, "zs_snapshot")
+            out = self.torch.empty((n, L["rec_bytes"]), dtype=self.torch.uint8, device=self.device)
+        self._check_records(out, "snapshot", n, L)
+        self._call("zs_snapshot", _ptr(idx), n, _ptr(out), self._stream())
         return out[:n]
 
     def restore(self, rec, src=None, dst=None, check=True):
@@ -487,8 +403,8 @@ class Engine(object):
         a repeated destination, lengths that differ); check=False is the asynchronous path, on which the kernel
         skips out-of-range entries and distinct destinations are the caller's contract."""
         t = self.torch
-        self._check_snapshot(rec, "restore")
-        s, d = self._index(src, "restore"), self._index(dst, "restore")
+        self._check_records(rec, "restore", 0, self.snapshot_layout())
+        s, d = as_index(t, src, self.device, "restore"), as_index(t, dst, self.device, "restore")
         n = int(s.shape[0]) if s is not None else int(d.shape[0]) if d is not None else int(rec.shape[0])
         if s is not None and d is not None and s.shape[0] != d.shape[0]:
             raise ValueError("restore: src and dst differ in length")
@@ -501,9 +417,7 @@ class Engine(object):
                 raise ValueError("restore: a record outside [0, %d) or an env outside [0, %d)" % (rec.shape[0], self.N))
             if dup:
                 raise ValueError("restore: a destination env is repeated")
-        rc = self.L.zs_restore(self.h, _ptr(rec), int(rec.shape[1]), int(rec.shape[0]), _ptr(s), _ptr(d), n, self._stream())
-        if rc:
-            _raise(self.L, rc, "zs_restore")
+        self._call("zs_restore", _ptr(rec), int(rec.shape[1]), int(rec.shape[0]), _ptr(s), _ptr(d), n, self._stream())
 
     # -- per-env zombie counts and time limits (zs_env_params_*; a config with FLAG_ENV_PARAMS) -------------------
     def set_env_params(self, params, envs=None, check=True):
@@ -520,61 +434,33 @@ class Engine(object):
         p = t.as_tensor(params)
         if p.dim() != 2 or p.shape[1] != 3 or p.dtype in (t.bool, t.float16, t.float32, t.float64):
             raise ValueError("set_env_params: params are an integer tensor [n, 3] or a dict of %s" % (_abi.ENV_PARAMS,))
-        p = self._as_int32(p)
-        idx = envs
-        if idx is not None:
-            idx = t.as_tensor(idx)
-            if idx.dim() != 1 or idx.dtype in (t.bool, t.float16, t.float32, t.float64):
-                raise ValueError("set_env_params: envs is a 1-D integer tensor or sequence")
-            idx = self._as_int32(idx)
+        p = _to_int32(t, p, self.device)
+        idx = as_index(t, envs, self.device, "set_env_params: envs")
         if idx is not None and idx.shape[0] != p.shape[0]:
             raise ValueError("set_env_params: %d envs for %d triples" % (idx.shape[0], p.shape[0]))
-        rc = self.L.zs_env_params_set(self.h, _ptr(idx), int(p.shape[0]), _ptr(p), self._stream())
-        if rc:
-            _raise(self.L, rc, "zs_env_params_set")
+        self._call("zs_env_params_set", _ptr(idx), int(p.shape[0]), _ptr(p), self._stream())
         if not check:
             return
         refused = C.c_uint32(0)  # reads OVF_PARAM_RANGE and clears that bit alone (one synchronisation)
-        rc = self.L.zs_env_params_check(self.h, C.byref(refused), self._stream())
-        if rc:
-            _raise(self.L, rc, "zs_env_params_check")
+        self._call("zs_env_params_check", C.byref(refused), self._stream())
         if refused.value:
             raise ValueError("set_env_params: an env outside [0, %d) or a value outside its range (caps: the "
                              "config's counts; max_episode_steps >= 0); the other entries were applied" % self.N)
-
-    def _as_int32(self, x):
-        """An integer tensor as a contiguous int32 device tensor; a value int32 does not hold becomes -1 (no env, no
-        count and no limit is -1: the device refuses the entry) instead of wrapping into range.  No synchronisation."""
-        t = self.torch
-        x = x.to(self.device)
-        if x.dtype != t.int32:
-            x = x.to(t.int64)
-            x = t.where((x < -2 ** 31) | (x > 2 ** 31 - 1), t.full_like(x, -1), x)
-        return x.to(t.int32).contiguous()
 
     def env_params(self, current=False, out=None):
         """int32 [N, 3]: every env's (initial_zombies, minimum_zombies, max_episode_steps), the triple its next
         reset takes up, or with current=True the triple of its running episode (zs_env_params_get)."""
         t = self.torch
         o = t.empty((self.N, 3), dtype=t.int32, device=self.device) if out is None else out
-        if o.dtype != t.int32 or tuple(o.shape) != (self.N, 3) or not o.is_contiguous() or o.device != self.device:
-            raise ValueError("env_params: out is a contiguous int32 tensor [%d, 3] on %s" % (self.N, self.device))
-        rc = self.L.zs_env_params_get(self.h, 1 if current else 0, _ptr(o), self._stream())
-        if rc:
-            _raise(self.L, rc, "zs_env_params_get")
+        check_tensor(o, "env_params: out", t.int32, self.device, self.N, (3,))
+        self._call("zs_env_params_get", 1 if current else 0, _ptr(o), self._stream())
         return o
 
     # -- per-env episode statistics (zs_episode_stats_*; a config with FLAG_EPISODE_STATS) -------------------------
     def episode_stats_layout(self):
         """zs_episode_stats_layout as a dict: "R" (reward slots per env), "last_words", "tot_words" (8 each), and the
         byte offset "ep_run" and size "ep_bytes" of the running part's section of the handle's snapshot record."""
-        if getattr(self, "_epl", None) is None:
-            out = (C.c_int32 * 8)()
-            rc = self.L.zs_episode_stats_layout(self.h, out)
-            if rc:
-                _raise(self.L, rc, "zs_episode_stats_layout")
-            self._epl = dict(zip(("R", "last_words", "tot_words", "ep_run", "ep_bytes"), [int(v) for v in out]))
-        return self._epl
+        return self._layout("zs_episode_stats_layout")
 
     def episode_stats(self, mask=None, out=None):
         """The episode statistics as a dict of five device tensors (zs_episode_stats_get, one launch, no
@@ -589,59 +475,38 @@ class Engine(object):
         if out is None:
             out = {k: t.zeros((self.N, w), dtype=dt, device=self.device) for k, (dt, w) in shapes.items()}
         for k, (dt, w) in shapes.items():
-            o = out.get(k)
-            if o is not None and (o.dtype != dt or tuple(o.shape) != (self.N, w) or not o.is_contiguous() or
-                                  o.device != self.device):
-                raise ValueError("episode_stats: %s is a contiguous %s tensor [%d, %d] on %s" % (k, dt, self.N, w, self.device))
-        rc = self.L.zs_episode_stats_get(self.h, _ptr(mask), _ptr(out.get("run_ret")), _ptr(out.get("last_ret")),
-                                         _ptr(out.get("sum_ret")), _ptr(out.get("last")), _ptr(out.get("tot")), self._stream())
-        if rc:
-            _raise(self.L, rc, "zs_episode_stats_get")
+            if out.get(k) is not None:
+                check_tensor(out[k], "episode_stats: " + k, dt, self.device, self.N, (w,))
+        self._call("zs_episode_stats_get", _ptr(mask), *[_ptr(out.get(k)) for k in shapes], self._stream())
         return out
 
     def clear_episode_stats(self, mask=None):
         """Zero the last finished episode and the totals of every env (or where the uint8 device tensor `mask` is
         nonzero); the running returns stay (zs_episode_stats_clear)."""
-        rc = self.L.zs_episode_stats_clear(self.h, _ptr(mask), self._stream())
-        if rc:
-            _raise(self.L, rc, "zs_episode_stats_clear")
+        self._call("zs_episode_stats_clear", _ptr(mask), self._stream())
 
     # -- frames of the envs (zs_render*; a config with FLAG_RENDER) ------------------------------------------------
     def render_layout(self):
         """zs_render_layout as a dict: "height", "width", "frame_bytes", "cell", "mask", "palette", "body_bytes" (the
         body colours' bytes per env) and "body_col" (their offset in the handle's snapshot record)."""
-        if getattr(self, "_rnl", None) is None:
-            out = (C.c_int32 * 8)()
-            rc = self.L.zs_render_layout(self.h, out)
-            if rc:
-                _raise(self.L, rc, "zs_render_layout")
-            self._rnl = dict(zip(("height", "width", "frame_bytes", "cell", "mask", "palette", "body_bytes", "body_col"),
-                                 [int(v) for v in out]))
-        return self._rnl
+        return self._layout("zs_render_layout")
 
     def render(self, envs=None, out=None):
         """Frames of the envs as a uint8 [n, 10 H, 10 W, 3] RGB device tensor (zs_render: one launch, no
-        synchronisation), pixel-exact to the map area of the reference's OpencvRenderer.  `envs`: an int32 device
-        tensor (or a sequence) of env indices, repeats allowed, default every env in order; an index outside [0, N)
-        leaves its frame as it is (zero in a tensor this call allocates).  `out`: a contiguous uint8 device tensor
+        synchronisation), pixel-exact to the map area of the reference's OpencvRenderer.  `envs`: an integer
+        tensor or sequence of env indices (as_index), repeats allowed, default every env in order; an index outside
+        [0, N) leaves its frame as it is (zero in a tensor this call allocates).  `out`: a contiguous uint8 device tensor
         [m, 10 H, 10 W, 3] to draw into; with m < n only the first m entries are drawn.  Without `out` the frames are
         allocated zero-filled on every call (1.2 MB per bridge64 frame: a memset of the whole tensor ahead of the
         draw), so a caller that draws many envs or draws every step passes its own `out`."""
         t = self.torch
         L = self.render_layout()
-        if envs is not None and not t.is_tensor(envs):
-            envs = t.as_tensor(np.asarray(envs, dtype=np.int32).reshape(-1), device=self.device)
-        if envs is not None and (envs.dtype != t.int32 or envs.dim() != 1 or not envs.is_contiguous() or envs.device != self.device):
-            raise ValueError("render: envs is a contiguous int32 tensor [n] on %s" % (self.device,))
+        envs = as_index(t, envs, self.device, "render: envs")
         n = self.N if envs is None else int(envs.numel())
         if out is None:
             out = t.zeros((n, L["height"], L["width"], 3), dtype=t.uint8, device=self.device)
-        if (out.dtype != t.uint8 or out.dim() != 4 or tuple(out.shape[1:]) != (L["height"], L["width"], 3) or
-                not out.is_contiguous() or out.device != self.device):
-            raise ValueError("render: out is a contiguous uint8 tensor [m, %d, %d, 3] on %s" % (L["height"], L["width"], self.device))
-        rc = self.L.zs_render(self.h, _ptr(envs), n, _ptr(out), int(out.shape[0]), self._stream())
-        if rc:
-            _raise(self.L, rc, "zs_render")
+        check_tensor(out, "render: out", t.uint8, self.device, 0, (L["height"], L["width"], 3), at_least=True)
+        self._call("zs_render", _ptr(envs), n, _ptr(out), int(out.shape[0]), self._stream())
         return out
 
     def set_render_atlas(self, masks, palette):
@@ -649,27 +514,21 @@ class Engine(object):
         of render.SHAPES, `palette` uint8 [8, 3] RGB (render.default_atlas() gives the reference's)."""
         m = np.ascontiguousarray(np.asarray(masks, dtype=np.uint32).reshape(5, 4))
         pal = np.ascontiguousarray(np.asarray(palette, dtype=np.uint8).reshape(8, 3))
-        rc = self.L.zs_render_sprites(self.h, _np_ptr(m), _np_ptr(pal))
-        if rc:
-            _raise(self.L, rc, "zs_render_sprites")
+        self._call("zs_render_sprites", _np_ptr(m), _np_ptr(pal))
 
     def gen_actions(self, step, n_discrete, out=None):
         o = self.actions if out is None else out
-        rc = self.L.zs_gen_actions(self.h, int(step), int(n_discrete), _ptr(o), self._stream())
-        if rc:
-            _raise(self.L, rc, "zs_gen_actions")
+        self._call("zs_gen_actions", int(step), int(n_discrete), _ptr(o), self._stream())
         return o
 
     def profile(self, enable=True):
         """Bracket every k_tick / k_obs launch with HIP events on its stream."""
-        self.L.zs_profile(self.h, 1 if enable else 0)
+        self._call("zs_profile", 1 if enable else 0)
 
     def profile_read(self):
         """Per-kernel totals: tick_ms/tick_n, obs_ms/obs_n, reset_ms/reset_n, respawn_ms/respawn_n."""
         out = (C.c_double * 8)()
-        rc = self.L.zs_profile_read(self.h, out)
-        if rc:
-            _raise(self.L, rc, "zs_profile_read")
+        self._call("zs_profile_read", out)
         return {"tick_ms": out[0], "tick_n": int(out[1]), "obs_ms": out[2], "obs_n": int(out[3]),
                 "reset_ms": out[4], "reset_n": int(out[5]), "respawn_ms": out[6], "respawn_n": int(out[7])}
 
@@ -677,44 +536,34 @@ class Engine(object):
         """The launch configuration the engine chose (zs_describe), as a dict."""
         import json
         buf = C.create_string_buffer(2048)
-        rc = self.L.zs_describe(self.h, buf, len(buf))
-        if rc:
-            _raise(self.L, rc, "zs_describe")
+        self._call("zs_describe", buf, len(buf))
         return json.loads(buf.value.decode())
 
     def debug_stamps(self, n=5):
         """Per-phase k_tick cycle sums / maxima (diagnostic -DZS_STAMPS build only)."""
         ssum = np.zeros(n, dtype=np.uint64)
         smax = np.zeros(n, dtype=np.uint64)
-        rc = self.L.zs_debug_stamps(self.h, C.c_void_p(ssum.ctypes.data), C.c_void_p(smax.ctypes.data), n)
-        if rc:
-            _raise(self.L, rc, "zs_debug_stamps")
+        self._call("zs_debug_stamps", C.c_void_p(ssum.ctypes.data), C.c_void_p(smax.ctypes.data), n)
         return ssum, smax
 
     def debug_stamps_wg(self, n_wgs, n_phase):
         """Per-workgroup phase cycles of the step launches since the last stamps read, shape [n_wgs, n_phase]
         (diagnostic -DZS_STAMPS build only)."""
         out = np.zeros((n_wgs, n_phase), dtype=np.uint64)
-        rc = self.L.zs_debug_stamps_wg(self.h, C.c_void_p(out.ctypes.data), n_wgs, n_phase)
-        if rc:
-            _raise(self.L, rc, "zs_debug_stamps_wg")
+        self._call("zs_debug_stamps_wg", C.c_void_p(out.ctypes.data), n_wgs, n_phase)
         return out
 
     def debug_timeline(self, n):
         """Start / end s_memrealtime (100 MHz) of the first n workgroups of the last fused step launch,
         shape [n, 2] (diagnostic -DZS_STAMPS build only)."""
         out = np.zeros((n, 2), dtype=np.uint64)
-        rc = self.L.zs_debug_timeline(self.h, C.c_void_p(out.ctypes.data), n)
-        if rc:
-            _raise(self.L, rc, "zs_debug_timeline")
+        self._call("zs_debug_timeline", C.c_void_p(out.ctypes.data), n)
         return out
 
     def debug_lists(self):
         """(pending-reset count of list 0, of list 1, deferred-respawn count, parity drained next)."""
         out = (C.c_int32 * 4)()
-        rc = self.L.zs_debug_lists(self.h, out, self._stream())
-        if rc:
-            _raise(self.L, rc, "zs_debug_lists")
+        self._call("zs_debug_lists", out, self._stream())
         return tuple(int(v) for v in out)
 
     def death_log(self, env):
@@ -722,9 +571,7 @@ class Engine(object):
         a list of (slot, serial, x, y, life).  Needs a config with FLAG_DEATH_LOG."""
         out = (C.c_int32 * (5 * max(1, self.E)))()
         n = C.c_int32(0)
-        rc = self.L.zs_death_log(self.h, int(env), out, int(self.E), C.byref(n), self._stream())
-        if rc:
-            _raise(self.L, rc, "zs_death_log")
+        self._call("zs_death_log", int(env), out, int(self.E), C.byref(n), self._stream())
         return decode_death_log(np.frombuffer(out, dtype=np.int32), n.value, self.E)
 
     def action_log(self, env):
@@ -735,21 +582,13 @@ class Engine(object):
         before the raising one, in dict order."""
         out = (C.c_int32 * (2 * max(1, self.E)))()
         n = C.c_int32(0)
-        rc = self.L.zs_action_log(self.h, int(env), out, int(self.E), C.byref(n), self._stream())
-        if rc:
-            _raise(self.L, rc, "zs_action_log")
+        self._call("zs_action_log", int(env), out, int(self.E), C.byref(n), self._stream())
         return decode_action_log(np.frombuffer(out, dtype=np.int32), n.value, self.E)
 
     # -- the drop-ins' per-call path (zs_host_*): one copy in, one copy out, one synchronisation ----------
     def host_layout(self):
         """Word offsets of a zs_host_* record's sections (zs_host_layout)."""
-        if getattr(self, "_hl", None) is None:
-            out = (C.c_int32 * 8)()
-            rc = self.L.zs_host_layout(self.h, out)
-            if rc:
-                _raise(self.L, rc, "zs_host_layout")
-            self._hl = dict(zip(("words", "rew", "alog", "dlog", "state", "obs", "obs_bytes", "R"), [int(v) for v in out]))
-        return self._hl
+        return self._layout("zs_host_layout")
 
     def host_record(self):
         """A fresh record buffer for one zs_host_* call over all N envs (int32 [N][words])."""
@@ -759,45 +598,31 @@ class Engine(object):
         """zs_host_step: actions int32 [N, A, 3] (host), rng [N][625] uint32 words (random.getstate() form;
         a numpy array or packed bytes) or None, rec from host_record() (filled)."""
         a = np.ascontiguousarray(actions, dtype=np.int32)
-        rc = self.L.zs_host_step(self.h, C.c_void_p(a.ctypes.data), _np_ptr(rng), C.c_void_p(rec.ctypes.data),
-                                 self._stream())
-        if rc:
-            _raise(self.L, rc, "zs_host_step")
+        self._call("zs_host_step", C.c_void_p(a.ctypes.data), _np_ptr(rng), C.c_void_p(rec.ctypes.data), self._stream())
         return rec
 
     def host_reset(self, rng, rec):
         """zs_host_reset: every env rebuilt (Game.__initialize_world__), record filled.  On ZS_ENOSPACE the
         record still holds the envs' streams (the caller moves them back before re-raising)."""
-        rc = self.L.zs_host_reset(self.h, _np_ptr(rng), C.c_void_p(rec.ctypes.data), self._stream())
-        if rc:
-            _raise(self.L, rc, "zs_host_reset")
+        self._call("zs_host_reset", _np_ptr(rng), C.c_void_p(rec.ctypes.data), self._stream())
         return rec
 
     def host_observe(self, rec):
-        rc = self.L.zs_host_observe(self.h, C.c_void_p(rec.ctypes.data), self._stream())
-        if rc:
-            _raise(self.L, rc, "zs_host_observe")
+        self._call("zs_host_observe", C.c_void_p(rec.ctypes.data), self._stream())
         return rec
 
     def get_state(self, env):
         buf = np.zeros(self.state_words, dtype=np.int32)
-        rc = self.L.zs_get_state(self.h, int(env), C.c_void_p(buf.ctypes.data), self._stream())
-        if rc:
-            _raise(self.L, rc, "zs_get_state")
+        self._call("zs_get_state", int(env), C.c_void_p(buf.ctypes.data), self._stream())
         return StateView(self, buf)
 
     def set_state(self, env, view):
-        rc = self.L.zs_set_state(self.h, int(env), C.c_void_p(view.buf.ctypes.data), self._stream())
-        if rc:
-            _raise(self.L, rc, "zs_set_state")
-
+        self._call("zs_set_state", int(env), C.c_void_p(view.buf.ctypes.data), self._stream())
 
     def overflow(self, clear=False):
         """Sticky range flags (_abi.OVF_INT16 | OVF_INT32 | OVF_PARAM_RANGE) of every env since creation / the last clear."""
         f = C.c_uint32(0)
-        rc = self.L.zs_overflow(self.h, C.byref(f), 1 if clear else 0, self._stream())
-        if rc:
-            _raise(self.L, rc, "zs_overflow")
+        self._call("zs_overflow", C.byref(f), 1 if clear else 0, self._stream())
         return int(f.value)
 
     def check_lossless(self):
@@ -812,16 +637,12 @@ class Engine(object):
     def get_rng(self, env):
         """(mt[624] uint32, index) of env's MT19937 stream, CPython getstate() form."""
         buf = np.zeros(625, dtype=np.uint32)
-        rc = self.L.zs_get_rng(self.h, int(env), C.c_void_p(buf.ctypes.data), self._stream())
-        if rc:
-            _raise(self.L, rc, "zs_get_rng")
+        self._call("zs_get_rng", int(env), C.c_void_p(buf.ctypes.data), self._stream())
         return buf
 
     def set_rng(self, env, state):
         buf = np.ascontiguousarray(np.asarray(state, dtype=np.uint32).reshape(625))
-        rc = self.L.zs_set_rng(self.h, int(env), C.c_void_p(buf.ctypes.data), self._stream())
-        if rc:
-            _raise(self.L, rc, "zs_set_rng")
+        self._call("zs_set_rng", int(env), C.c_void_p(buf.ctypes.data), self._stream())
 
     def load_python_random(self, env, rnd=None):
         """Move a `random.Random` (default: the module-global one) state into env."""

@@ -18,7 +18,7 @@ for a centralised learner (`gather_observations`, RCCL all-gather over xGMI).
 """
 from . import _abi
 from .actions import DISCRETE_TRIPLES
-from .engine import Engine
+from .engine import Engine, as_index
 
 
 def shard_range(total_envs, rank, world):
@@ -242,7 +242,7 @@ class BatchedZombsole(object):
             n = snap.shape[0] if src is None else len(src)
             mask[:min(int(n), eng.N)] = 1
         else:
-            d = eng._index(dst, "restore").long()
+            d = as_index(t, dst, eng.device, "restore").long()
             mask[d[(d >= 0) & (d < eng.N)]] = 1
         if self.engine.masks is not None:  # the written envs' action masks, beside their observations
             eng.action_mask(mask)

@@ -476,3 +476,39 @@ def test_refusals_launch_nothing():
         eng.set_state(e, st)
     viewer.close()
     sim.close()
+
+
+def test_an_index_beyond_int32_names_nothing():
+    """An index that int32 does not hold is no record and no env (engine.as_index turns it into -1): restore refuses
+    it under check=True and skips it under check=False, render leaves its frame alone.  It used to wrap into range
+    (record 2**32 + 1 was record 1), and render refused every tensor that was not int32."""
+    import torch
+
+    from libzombsole_amd.engine import Engine
+    mk, n, nd, _ = SHAPES["wall_hp_i16"]  # the smallest map of SHAPES
+    seeds = [4000 + 3 * i for i in range(n)]
+    eng = Engine(mk(n), device=0)
+    eng.seed(seeds)
+    eng.reset()
+    for t in range(1, 4):
+        eng.gen_actions(t, nd)
+        eng.step()
+    rec = eng.snapshot().clone()
+    before = eng.snapshot([0]).clone()
+    assert not torch.equal(rec[1], before[0]), "record 1 differs from env 0: a wrapped index would show"
+    far = torch.tensor([2 ** 32 + 1], dtype=torch.int64)
+    with pytest.raises(ValueError, match="outside"):
+        eng.restore(rec, src=far, dst=[0], check=True)
+    eng.restore(rec, src=far, dst=[0], check=False)
+    torch.cuda.synchronize()
+    assert torch.equal(eng.snapshot([0]), before)
+    eng.close()
+    ren = Engine(mk(n, render=True), device=0)
+    ren.seed(seeds)
+    ren.reset()
+    want = ren.render([0]).clone()
+    out = torch.full((2,) + tuple(want.shape[1:]), 0x5A, dtype=torch.uint8, device=ren.device)
+    ren.render(envs=torch.tensor([0, 2 ** 32 + 1], dtype=torch.int64), out=out)
+    torch.cuda.synchronize()
+    assert torch.equal(out[0], want[0]) and bool((out[1] == 0x5A).all())
+    ren.close()
