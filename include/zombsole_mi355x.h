@@ -465,6 +465,40 @@ int zs_entity_obs_layout(const zs_handle* h, int32_t kz, int32_t kp, int32_t out
 int zs_entity_obs(zs_handle* h, const uint8_t* env_mask_dev, int32_t kz, int32_t kp, void* out_dev, void* stream);
 int zs_entity_obs_bind(zs_handle* h, void* out_dev_or_null, int32_t kz, int32_t kp);
 
+/* ---- scripted policies for agent slots: a launch that writes the bots' actions as agent triples -------------
+ * out_dev is int32 [N][num_agents][3], triples in zs_step's action form (ZS_ACT_*, dx, dy), 4-byte aligned (else
+ * ZS_EINVAL); policy_dev is uint8 [N][num_agents], one ZS_PILOT_* code per agent.  Each row is computed from the env's
+ * current world, the one its observation shows (an env pending its reset: the terminal world):
+ *   ZS_PILOT_NONE        the row is not written: a caller's own triple in it survives
+ *   ZS_PILOT_TERMINATOR  players/terminator.py with the agent's own weapon.  z = the closest present zombie, ties
+ *                        broken by the reference's dict order.  No zombie: (ZS_ACT_HEAL, 0, 0).  z within the weapon's
+ *                        range: (ZS_ACT_ATTACK_CLOSEST, 0, 0).  Else (dx, dy) = the adjacent cell closest to z, the
+ *                        first minimum over (0,1), (0,-1), (1,0), (-1,0): (ZS_ACT_HEAL, dx, dy) when an agent or bot
+ *                        stands there, (ZS_ACT_ATTACK, dx, dy) when any other thing does (a zombie; an obstacle
+ *                        whatever its life), else (ZS_ACT_MOVE, dx, dy), a cell outside the map included
+ *   ZS_PILOT_SNIPER      players/sniper.py: (ZS_ACT_ATTACK_CLOSEST, 0, 0)
+ *   ZS_PILOT_TROLL       players/troll.py: (ZS_ACT_HEAL, 0, 0)
+ *   any other code       (ZS_ACT_IDLE, 0, 0), and the sticky ZS_OVF_PARAM_RANGE bit of zs_overflow's word is raised
+ * An agent of nonzero code that is not in the world gets (ZS_ACT_IDLE, 0, 0).  Given such a triple, zs_step does for
+ * the agent exactly what the reference's bot of that class does in its place.  No policy draws from the env's stream.
+ *
+ * zs_autopilot: one launch on `stream` for the envs whose env_mask_dev byte is nonzero (NULL = all); other envs' rows
+ * are untouched.
+ * zs_autopilot_bind: while a policy and an output are bound (both non-NULL; both NULL unbinds), every zs_step ends with
+ * a launch of all envs, after the observation / tail launch and the bound mask and entity launches and before the
+ * episode statistics, eagerly and for each step of zs_step_graph(_n).  The policy tensor's contents may change between
+ * steps and graph replays.  out_dev may be the action buffer the steps read: step t's last launch then writes the rows
+ * step t + 1 takes (the closed loop; with zs_step_graph(_n) pass n_discrete = 0, else the generated policy overwrites
+ * them).  Binding other buffers or NULL drops the cached graphs.  The buffers must outlive the binding.
+ * Both calls: ZS_EINVAL on a NULL argument, ZS_ESTATE on a viewer handle (its observation-state records carry no dict
+ * order, which the closest zombie's tie-break reads). */
+#define ZS_PILOT_NONE 0
+#define ZS_PILOT_TERMINATOR 1
+#define ZS_PILOT_SNIPER 2
+#define ZS_PILOT_TROLL 3
+int zs_autopilot(zs_handle* h, const uint8_t* env_mask_dev, const uint8_t* policy_dev, int32_t* out_dev, void* stream);
+int zs_autopilot_bind(zs_handle* h, const uint8_t* policy_dev_or_null, int32_t* out_dev_or_null);
+
 /* ---- per-env zombie counts and time limits (ZS_FLAG_ENV_PARAMS) ----------------------------------------
  * A flagged handle holds, per env, the triple (initial_zombies, minimum_zombies, max_episode_steps) twice: the
  * NEXT triple and the CURRENT one.  After zs_create both equal the config's values, and until the first
@@ -589,6 +623,8 @@ int zs_profile_read(zs_handle* h, double out[8]);
  * (ZS_FLAG_EPISODE_STATS); "render" whether it draws frames (ZS_FLAG_RENDER), "render_grid" k_render's workgroups
  * per frame and "render_block" their threads (0 without the flag); "entity_obs_bound" whether an entity-observation
  * buffer is bound (zs_entity_obs_bind) and "entity_kz", "entity_kp" its K values (0 when none);
+ * "autopilot_kernel", "autopilot_grid", "autopilot_block" the scripted-policy launch (zs_autopilot) and
+ * "autopilot_bound" whether a policy is bound (zs_autopilot_bind);
  * "step_tail_launch" the launch that carried the tail of the last zs_step queued or captured: the observation kernel,
  * or "k_tail" when the step launch wrote the observations itself or obs_dev was NULL ("" before any step).
  * Returns ZS_OK. */

@@ -246,6 +246,8 @@ ABI = {
     "zs_entity_obs_layout": [_vp, _i32, _i32, _pi32],
     "zs_entity_obs": [_vp, _vp, _i32, _i32, _vp, _vp],
     "zs_entity_obs_bind": [_vp, _vp, _i32, _i32],
+    "zs_autopilot": [_vp, _vp, _vp, _vp, _vp],
+    "zs_autopilot_bind": [_vp, _vp, _vp],
     "zs_env_params_set": [_vp, _vp, _i32, _vp, _vp],
     "zs_env_params_get": [_vp, _i32, _vp, _vp],
     "zs_env_params_check": [_vp, _pu32, _vp],

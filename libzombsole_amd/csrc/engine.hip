@@ -6,7 +6,8 @@
 // in LDS), k_respawn (deferred zombie respawns, one wave per env) and the observation kernel (zs_obs.hpp: k_obs_ring /
 // k_obs_pipe persistent store streams, k_obs_gather for large maps, k_obs in general), else k_tail, then k_action_mask
 // (zs_mask.hpp) when a mask buffer is bound and k_entity_obs (k_entity_obs.hip, zs_entity_obs.hpp) when an entity
-// buffer is.  With a null obs_dev no grid observation is written and k_tail ends the step.  zs_step_graph replays a step as a hipGraph.  The small helpers behind the
+// buffer is, then k_autopilot (k_autopilot.hip, zs_autopilot.hpp) when a policy is bound.  With a null obs_dev no grid
+// observation is written and k_tail ends the step.  zs_step_graph replays a step as a hipGraph.  The small helpers behind the
 // ABI (seeding, the policy stream, the state views, the drop-ins' per-call records) are k_state.hip's; the per-env
 // record movers (observation-state records, zs_obs_state.hpp; snapshot records, zs_snapshot.hpp and zs_record.hpp) are
 // k_records.hip's; k_env_params.hip scatters per-env zombie counts and time limits (ZS_FLAG_ENV_PARAMS); a
@@ -29,6 +30,7 @@
 #include "zs_record.hpp"
 #include "zs_mask.hpp"  // the mask launch's geometry (zs_describe); the kernel is k_mask.hip's
 #include "zs_entity_obs.hpp"  // the entity observation's layout and launcher; the kernel is k_entity_obs.hip's
+#include "zs_autopilot.hpp"  // the scripted policies' launcher and geometry; the kernel is k_autopilot.hip's
 #include "zs_episode.hpp"  // the running part's columns (ZS_EP_RUN_COLS); the kernels are k_episode.hip's
 
 // ===========================================================================
@@ -112,6 +114,9 @@ struct zs_handle {
     int32_t* d_obj_xy = nullptr;
     void* ent_bound = nullptr;
     int ent_kz = 0, ent_kp = 0;
+    // zs_autopilot_bind: every zs_step ends with an autopilot launch of this policy (uint8 [N][A]) into these triples
+    const uint8_t* pilot_policy = nullptr;
+    int32_t* pilot_out = nullptr;
     const char* step_last = "";  // the launch that carried the tail of the last zs_step queued or captured (zs_describe)
     // ZS_FLAG_EPISODE_STATS: the statistics' arrays (k_episode.hip's argument; ep.run null without the flag) and the
     // [N] byte row the tick writes its reset flags to when the caller passes no reset_dev
@@ -872,6 +877,9 @@ extern "C" int zs_step(zs_handle* h, const int32_t* actions_dev, void* obs_dev, 
         const EntityArgs g = {h->ent_kz, h->ent_kp, d.nobj, h->d_obj_xy};
         LAUNCHCHK("k_entity_obs", launch_entity_obs(s, d, g, nullptr, h->ent_bound));
     }
+    //    ... and a bound autopilot (zs_autopilot_bind): the scripted triples of that world.  Bound to the caller's action
+    //    buffer this is the closed loop: the rows the next step's tick reads
+    if (h->pilot_out) LAUNCHCHK("k_autopilot", launch_autopilot(s, d, nullptr, h->pilot_policy, h->pilot_out));
     // 5) ZS_FLAG_EPISODE_STATS: the step's rewards and flags into the running returns, a finished episode latched
     //    and counted (the terminal world stays until the next call's reset work)
     if (h->ep.run) LAUNCHCHK("k_episode_stats", launch_episode_stats(s, h->ep, rewards_dev, done_dev, trunc_dev, reset_dev));
@@ -955,6 +963,36 @@ extern "C" int zs_entity_obs_bind(zs_handle* h, void* out_dev_or_null, int32_t k
     h->ent_bound = out_dev_or_null;
     h->ent_kz = kz;
     h->ent_kp = kp;
+    return ZS_OK;
+}
+
+static int pilot_args_ok(const void* policy_dev, const void* out_dev) {
+    if (!policy_dev || !out_dev) return fail(ZS_EINVAL, "null argument");
+    if (((uintptr_t)out_dev & 3u) != 0) return fail(ZS_EINVAL, "the autopilot's triples must be 4-byte aligned");
+    return ZS_OK;
+}
+
+// Scripted triples of the current state (zs_autopilot.hpp), int32 [N][A][3] under the policy codes uint8 [N][A].  Not on
+// a viewer handle: the observation-state record carries no order row, which the closest zombie's tie-break reads.
+extern "C" int zs_autopilot(zs_handle* h, const uint8_t* env_mask_dev, const uint8_t* policy_dev, int32_t* out_dev, void* stream) {
+    if (!h) return fail(ZS_EINVAL, "null handle");
+    TRY(pilot_args_ok(policy_dev, out_dev));
+    NOT_ON_VIEWER(h, "zs_autopilot");
+    ENTER(h, stream, s);
+    HIPCHK(launch_autopilot(s, h->d, env_mask_dev, policy_dev, out_dev));
+    return ZS_OK;
+}
+
+extern "C" int zs_autopilot_bind(zs_handle* h, const uint8_t* policy_dev_or_null, int32_t* out_dev_or_null) {
+    if (!h) return fail(ZS_EINVAL, "null handle");
+    NOT_ON_VIEWER(h, "zs_autopilot_bind");
+    if (policy_dev_or_null || out_dev_or_null) {  // both, or neither (unbind)
+        TRY(pilot_args_ok(policy_dev_or_null, out_dev_or_null));
+    }
+    if (policy_dev_or_null == h->pilot_policy && out_dev_or_null == h->pilot_out) return ZS_OK;
+    TRY(drop_step_graphs(h));
+    h->pilot_policy = policy_dev_or_null;
+    h->pilot_out = out_dev_or_null;
     return ZS_OK;
 }
 
@@ -1398,14 +1436,15 @@ extern "C" int zs_describe(zs_handle* h, char* buf, int32_t len) {
              "\"obs_kernel_masked\": \"%s\", \"obs_encoders\": \"%s\", \"mask_kernel\": \"k_action_mask\", "
              "\"mask_grid\": %u, \"mask_block\": %d, \"mask_bound\": %d, \"env_params\": %d, \"episode_stats\": %d, "
              "\"render\": %d, \"render_grid\": %d, \"render_block\": %d, \"entity_obs_bound\": %d, \"entity_kz\": %d, "
-             "\"entity_kp\": %d, \"step_tail_launch\": \"%s\"}",
+             "\"entity_kp\": %d, \"autopilot_kernel\": \"k_autopilot\", \"autopilot_grid\": %u, \"autopilot_block\": %d, "
+             "\"autopilot_bound\": %d, \"step_tail_launch\": \"%s\"}",
              d.N, d.E, p.G, p.fused ? "k_step" : "k_tick", p.lds, p.resident, p.rw_cap,
              d.fobs ? "step launch" : obs_kernel_name(kf.kind), h->reset_side,
              p.reset_lds, p.defer_respawn ? "k_respawn" : "tick", p.tick_waves, p.rw_step,
              d.par_exec, obs_kernel_name(h->obs.masked.kind), obs_encoders_name(kf), zs_mask_grid(d.N), ZS_MASK_BLOCK,
              h->mask_bound ? 1 : 0, (d.flags & ZS_FLAG_ENV_PARAMS) ? 1 : 0, h->ep.run ? 1 : 0, h->rn.body_col ? 1 : 0,
              h->rn.body_col ? h->rn.plan.bands : 0, h->rn.body_col ? ZS_RENDER_BLOCK : 0,
-             h->ent_bound ? 1 : 0, h->ent_kz, h->ent_kp, h->step_last);
+             h->ent_bound ? 1 : 0, h->ent_kz, h->ent_kp, zs_pilot_grid(d.N), ZS_PILOT_BLOCK, h->pilot_out ? 1 : 0, h->step_last);
     return ZS_OK;
 }
 

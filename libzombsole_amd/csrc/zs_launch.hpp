@@ -5,6 +5,7 @@
 //   k_obs_t.hip   once per observation dtype (-DZS_OBS_T=0/1/2): every observation kernel
 //   k_reset.hip   k_reset, k_respawn, k_list_filter
 //   k_mask.hip    k_action_mask (zs_mask.hpp)
+//   k_autopilot.hip  k_autopilot (zs_autopilot.hpp, with its launcher's declaration)
 //   k_env_params.hip  k_env_params, k_env_params_get, k_env_params_init, k_env_params_check (ZS_FLAG_ENV_PARAMS)
 //   k_episode.hip  k_episode_stats, k_episode_get, k_episode_clear (ZS_FLAG_EPISODE_STATS; zs_episode.hpp)
 //   k_render.hip  k_render, k_render_track (ZS_FLAG_RENDER; zs_render.hpp)

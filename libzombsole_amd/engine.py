@@ -173,6 +173,8 @@ class Engine(object):
         self.masks = None  # the bound action-mask tensor (bind_action_masks), uint8 [N, A, 8]
         self.entities = None  # the bound entity-observation tensor (bind_entity_obs), int16 [N, A, ROW]
         self.entity_k = None  # its (kz, kp)
+        self.pilot = None  # the bound scripted triples (bind_autopilot), int32 [N, A, 3]; self.actions when bound into it
+        self.pilot_policy = None  # the bound policy codes, uint8 [N, A]
 
     def close(self):
         if getattr(self, "h", None) and self.h.value:
@@ -342,6 +344,54 @@ class Engine(object):
         self.entities = buf
         self.entity_k = (int(kz), int(kp)) if buf is not None else None
         return buf
+
+    # -- scripted policies for agent slots (zs_autopilot*): the bots' decisions as agent triples, int32 [N, A, 3] -------
+    def policy_tensor(self, policy):
+        """`policy` as the uint8 [N, A] device tensor of codes (libzombsole_amd/autopilot.py): a policy's name or code
+        for every agent, or a tensor / array of codes that broadcasts to [N, A].  A uint8 [N, A] tensor on the device
+        comes back as it is."""
+        from . import autopilot
+        t = self.torch
+        if isinstance(policy, (str, int)):
+            return t.full((self.N, self.A), autopilot.policy_code(policy), dtype=t.uint8, device=self.device)
+        p = t.as_tensor(policy)
+        if p.dtype == t.uint8 and p.device == self.device and tuple(p.shape) == (self.N, self.A) and p.is_contiguous():
+            return p
+        if p.dtype == t.bool or p.is_floating_point() or p.is_complex():
+            raise ValueError("autopilot: policy codes are integers")
+        return p.to(self.device).to(t.uint8).expand(self.N, self.A).contiguous()
+
+    def autopilot(self, policy, mask=None, out=None):
+        """The scripted triples of the current state under `policy` (policy_tensor's forms), int32 [N, A, 3]
+        (zs_autopilot).  Rows of code 0 and envs where the uint8 device tensor `mask` is zero keep their values.  Into
+        `out` when given, else into a tensor this call allocates (zeroed)."""
+        t = self.torch
+        pol = self.policy_tensor(policy)
+        o = out if out is not None else t.zeros((self.N, self.A, 3), dtype=t.int32, device=self.device)
+        check_tensor(o, "autopilot: out", t.int32, self.device, self.N, (self.A, 3))
+        self._call("zs_autopilot", _ptr(mask), _ptr(pol), _ptr(o), self._stream())
+        return o
+
+    def bind_autopilot(self, policy, into_actions=False, out=None):
+        """Bind `policy` (policy_tensor's forms; None / False: unbind) so that every step(), step_graph() and
+        step_graphed() ends with an autopilot launch (zs_autopilot_bind) into self.pilot: a new tensor, `out`, or with
+        into_actions=True self.actions, the closed loop in which a step's last launch writes the rows the next step
+        reads.  self.pilot_policy is the bound uint8 [N, A] code tensor; writing into it changes the policy of the
+        following steps, graph replays included.  Returns self.pilot."""
+        t = self.torch
+        if policy is None or policy is False:
+            self._call("zs_autopilot_bind", None, None)
+            self.pilot = self.pilot_policy = None
+            return None
+        pol = self.policy_tensor(policy)
+        if into_actions:
+            out = self.actions
+        elif out is None:
+            out = t.zeros((self.N, self.A, 3), dtype=t.int32, device=self.device)
+        check_tensor(out, "bind_autopilot: out", t.int32, self.device, self.N, (self.A, 3))
+        self._call("zs_autopilot_bind", _ptr(pol), _ptr(out))
+        self.pilot, self.pilot_policy = out, pol
+        return out
 
     # -- observation-state records (zs_obs_state_*): what the encoders read of an env, a fraction of its observation
     def obs_state_layout(self):

@@ -100,6 +100,16 @@ class MultiagentZombsoleEnv(object):
         that is not in the world has all zeros (include/zombsole_mi355x.h, zs_action_mask)."""
         return self._core.action_masks()
 
+    def scripted_actions(self, policy="terminator"):
+        """Not in the reference: {agent_id: action dict} for every possible agent, the action the scripted policy (a
+        name, or one name or code per agent; libzombsole_amd/autopilot.py) takes for it on the current world.  An agent
+        that is not in the world idles (include/zombsole_mi355x.h, zs_autopilot)."""
+        from ..autopilot import policy_code, to_action_dict
+        if not isinstance(policy, (str, int)):
+            policy = [policy_code(p) for p in policy]
+        rows = self._core.scripted_triples(policy)
+        return {aid: to_action_dict(rows[i]) for i, aid in enumerate(self._ids)}
+
     def _process_single_agent_action(self, sp_action):
         coords = sp_action.get("parameter", [0, 0])
         return {"action_type": sp_action["action_type"], "parameter": coords}
@@ -178,6 +188,9 @@ class MultiAgentWrapper(object):
 
     def action_masks(self):
         return self.env.action_masks()
+
+    def scripted_actions(self, policy="terminator"):
+        return self.env.scripted_actions(policy)
 
     def close(self):
         self.env.close()

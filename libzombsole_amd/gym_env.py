@@ -81,6 +81,13 @@ class ZombsoleGymEnv(Env):
         succeed for the agent on the current world (include/zombsole_mi355x.h, zs_action_mask)."""
         return self._core.action_masks()[0]
 
+    def scripted_action(self, policy="terminator"):
+        """Not in the reference: the action dict the scripted policy ("terminator", "sniper", "troll";
+        libzombsole_amd/autopilot.py) takes for the agent on the current world; step() with it does what the
+        reference's bot of that class would do in the agent's place (include/zombsole_mi355x.h, zs_autopilot)."""
+        from .autopilot import to_action_dict
+        return to_action_dict(self._core.scripted_triples(policy)[0])
+
     def step(self, action):
         """gym_env.py:99-145: set_action, World.step, reward, respawn, obs, rules, end reward."""
         self.game.agents[0].set_action(action)

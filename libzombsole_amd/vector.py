@@ -68,7 +68,7 @@ class BatchedZombsole(object):
                  observation_surroundings_width=21, observation_position_encoding_style="channels",
                  agent_weapons="rifle", obs_dtype=None, autoreset=True, device=None, lanes_per_env=0,
                  action_masks=False, env_params=False, episode_stats=False, render=False, entity_obs=None,
-                 grid_obs=True):
+                 grid_obs=True, autopilot=None, autopilot_into_actions=False):
         if surface == "single":
             b = _abi.single_env_config(num_envs, rules_name, player_names, map_name, agent_id, initial_zombies,
                                        minimum_zombies, observation_scope, observation_position_encoding,
@@ -102,6 +102,45 @@ class BatchedZombsole(object):
         # grid_obs=False: no grid observation is allocated or written; the entity tensor is the observation
         if entity_obs is not None:
             self.engine.bind_entity_obs(True, int(entity_obs[0]), int(entity_obs[1]))
+        # autopilot="terminator" | "sniper" | "troll" | uint8 [N, A] codes: scripted triples bound the same way
+        # (libzombsole_amd/autopilot.py), refreshed at the same places.  autopilot_into_actions=True binds the engine's
+        # action buffer: a step's last launch writes the rows the next step reads
+        if autopilot is not None:
+            self.engine.bind_autopilot(autopilot, into_actions=bool(autopilot_into_actions))
+
+    @property
+    def scripted_actions(self):
+        """int32 [N, A, 3]: the engine's bound scripted triples for the world self.obs shows, rows of policy code 0 left
+        as they were.  Valid after every reset, step, restore / clone and load_checkpoint.  None without autopilot=."""
+        return self.engine.pilot
+
+    def set_autopilot(self, policy):
+        """Write the bound policy tensor (a name, a code, or codes that broadcast to [N, A]); no synchronisation.  The
+        next launch (the next step's last, or a reset / restore) decides with it."""
+        eng = self.engine
+        if eng.pilot_policy is None:
+            raise ValueError("set_autopilot: no autopilot is bound (BatchedZombsole(autopilot=...))")
+        if isinstance(policy, (str, int)):
+            from .autopilot import policy_code
+            eng.pilot_policy.fill_(policy_code(policy))
+        else:
+            eng.pilot_policy.copy_(self.torch.as_tensor(policy).to(eng.device).expand(eng.N, eng.A))
+
+    def step_scripted(self, graph=True):
+        """step(self.scripted_actions): every agent slot of nonzero code played by its scripted policy."""
+        if self.engine.pilot is None:
+            raise ValueError("step_scripted: no autopilot is bound (BatchedZombsole(autopilot=...))")
+        return self.step(self.engine.pilot, graph=graph)
+
+    def _refresh(self, mask=None):
+        """The bound side tensors of the envs whose mask byte is nonzero (None: all), after a call that is no step."""
+        eng = self.engine
+        if eng.masks is not None:
+            eng.action_mask(mask)
+        if eng.entities is not None:
+            eng.entity_obs(mask)
+        if eng.pilot is not None:
+            eng.autopilot(eng.pilot_policy, mask, out=eng.pilot)
 
     @property
     def entity_obs(self):
@@ -182,10 +221,7 @@ class BatchedZombsole(object):
 
     def reset(self, mask=None):
         self.engine.reset(mask)
-        if self.engine.masks is not None:
-            self.engine.action_mask(mask)
-        if self.engine.entities is not None:
-            self.engine.entity_obs(mask)
+        self._refresh(mask)
         return self._observation()
 
     def discrete_to_triples(self, ids):
@@ -235,7 +271,7 @@ class BatchedZombsole(object):
         grid_obs=False: the entity tensor, which is refreshed whenever one is bound)."""
         eng, t = self.engine, self.torch
         eng.restore(snap, src, dst, check=check)
-        if not observe and self.engine.masks is None and self.engine.entities is None:
+        if not observe and self.engine.masks is None and self.engine.entities is None and self.engine.pilot is None:
             return None
         mask = t.zeros(eng.N, dtype=t.uint8, device=eng.device)
         if dst is None:
@@ -244,10 +280,7 @@ class BatchedZombsole(object):
         else:
             d = as_index(t, dst, eng.device, "restore").long()
             mask[d[(d >= 0) & (d < eng.N)]] = 1
-        if self.engine.masks is not None:  # the written envs' action masks, beside their observations
-            eng.action_mask(mask)
-        if self.engine.entities is not None:
-            eng.entity_obs(mask)
+        self._refresh(mask)  # the written envs' action masks, entity rows and scripted triples, beside their observations
         if not observe:
             return None
         return eng.observe(mask) if eng.grid_obs else eng.entities
