@@ -465,6 +465,51 @@ int zs_entity_obs_layout(const zs_handle* h, int32_t kz, int32_t kp, int32_t out
 int zs_entity_obs(zs_handle* h, const uint8_t* env_mask_dev, int32_t kz, int32_t kp, void* out_dev, void* stream);
 int zs_entity_obs_bind(zs_handle* h, void* out_dev_or_null, int32_t kz, int32_t kp);
 
+/* ---- path-distance fields: walking distance to the objectives and to the zombies, per env -------------------
+ * A cell is free when it is inside the map and holds no present obstacle, whatever the obstacle's life (the rule of
+ * the entity observation's rays); entities never block.  A field is the 4-connected breadth-first distance over free
+ * cells from a set of source cells, in moves; a source cell that is not free is not a source.  ZS_NAV_OBJECTIVE: the
+ * sources are the map's objective cells (there may be none); ZS_NAV_ZOMBIES: the cells of the present zombie slots.
+ * `fields` is a bitmask of the two, F its popcount, the fields emitted in ascending bit order.  1 <= max_dist <=
+ * ZS_NAV_MAX_DIST: the search stops after that many levels and a cell not reached by then is unreachable, as blocked
+ * cells and cells outside the map are.  Every value is of the env's current world, the one its observation shows (an
+ * env pending its reset: the terminal world).
+ *
+ * Rows: out_dev is int16 [N][num_agents][F][8], 8-byte aligned.  Word 0 the distance at the agent's cell; words 1..4
+ * the distances at the cells the moves (0,1), (-1,0), (0,-1), (1,0) lead to, -1 where unreachable, blocked or outside
+ * the map; word 5 the smallest k whose neighbour distance is the minimum over the reachable neighbours, word 6 the
+ * smallest k at their maximum, both -1 when no neighbour is reachable; word 7 flags: bit 0 the agent is present, bit 1
+ * its own cell is a source.  An agent that is not in the world has an all-zero row.
+ * Full field: out_dev is uint16 [n][H][W], 2-byte aligned, 0xFFFF = unreachable or blocked.
+ *
+ * The search runs in the workgroup's LDS (csrc/zs_nav.hpp nav_plan): a map whose single-env image is larger than
+ * 64 KiB (28 * H * ceil(W / 32) + 8 * 5 * num_agents bytes, rounded up to 16) is refused with ZS_EINVAL by zs_nav_obs,
+ * zs_nav_field and zs_nav_bind; zs_create refuses no handle for it.
+ *
+ * zs_nav_plan: out[0] = F, out[1] = the row's words (8), out[2] = the word offset of field 0's row in an agent's block
+ * (0), out[3] = that of field 1's (8 when F = 2, else -1), out[4] = envs per workgroup, out[5] = threads per workgroup,
+ * out[6] = the workgroup's LDS bytes, out[7] = one env's image bytes; out[4..6] are 0 where the map is past the limit
+ * (the call itself succeeds).
+ * zs_nav_obs: one launch on `stream` for the envs whose env_mask_dev byte is nonzero (NULL = all); other envs' rows are
+ * untouched.  Any handle: a viewer's envs (zs_obs_state_unpack) hold everything the kernel reads.
+ * zs_nav_field: frame k < n of env env_idx_dev[k] (NULL: k) and the one field `field`; an entry outside [0, N) leaves
+ * its frame untouched; entries may repeat.  Any handle.
+ * zs_nav_bind: while a buffer is bound (non-NULL), every zs_step ends with a launch of all envs into it, after the
+ * observation / tail launch and the bound mask and entity launches and before a bound autopilot's, eagerly, for each
+ * step of zs_step_graph(_n) and through zs_host_step.  Binding another buffer, other fields, another max_dist or NULL
+ * drops the cached graphs.  A handle that never binds launches what it did before.  The buffer must outlive the
+ * binding.  ZS_ESTATE on a viewer handle.
+ * ZS_EINVAL before any launch: fields zero or with unknown bits, field not exactly one of the two bits, max_dist out of
+ * range, a misaligned buffer, n < 0. */
+#define ZS_NAV_OBJECTIVE 1
+#define ZS_NAV_ZOMBIES 2
+#define ZS_NAV_MAX_DIST 32766
+int zs_nav_plan(const zs_handle* h, int32_t fields, int32_t out[8]);
+int zs_nav_obs(zs_handle* h, const uint8_t* env_mask_dev, int32_t fields, int32_t max_dist, void* out_dev, void* stream);
+int zs_nav_field(zs_handle* h, const int32_t* env_idx_dev, int32_t n, int32_t field, int32_t max_dist, void* out_dev,
+                 void* stream);
+int zs_nav_bind(zs_handle* h, void* out_dev_or_null, int32_t fields, int32_t max_dist);
+
 /* ---- scripted policies for agent slots: a launch that writes the bots' actions as agent triples -------------
  * out_dev is int32 [N][num_agents][3], triples in zs_step's action form (ZS_ACT_*, dx, dy), 4-byte aligned (else
  * ZS_EINVAL); policy_dev is uint8 [N][num_agents], one ZS_PILOT_* code per agent.  Each row is computed from the env's
@@ -624,7 +669,9 @@ int zs_profile_read(zs_handle* h, double out[8]);
  * per frame and "render_block" their threads (0 without the flag); "entity_obs_bound" whether an entity-observation
  * buffer is bound (zs_entity_obs_bind) and "entity_kz", "entity_kp" its K values (0 when none);
  * "autopilot_kernel", "autopilot_grid", "autopilot_block" the scripted-policy launch (zs_autopilot) and
- * "autopilot_bound" whether a policy is bound (zs_autopilot_bind);
+ * "autopilot_bound" whether a policy is bound (zs_autopilot_bind); "nav_kernel", "nav_envs_per_wg", "nav_block",
+ * "nav_lds_bytes" the path-distance launch (zs_nav_obs; 0 where the map is past its plan's limit), "nav_bound" whether
+ * a buffer is bound (zs_nav_bind) and "nav_fields", "nav_max_dist" its arguments (0 when none);
  * "step_tail_launch" the launch that carried the tail of the last zs_step queued or captured: the observation kernel,
  * or "k_tail" when the step launch wrote the observations itself or obs_dev was NULL ("" before any step).
  * Returns ZS_OK. */

@@ -139,6 +139,9 @@ LAYOUT_KEYS = {
 }
 
 ENTITY_KMAX, ENTITY_RAY_CAP = 16, 16
+# path-distance fields (csrc/zs_nav.hpp): the field bits, the largest cap, the words of zs_nav_plan's out[]
+NAV_OBJECTIVE, NAV_ZOMBIES, NAV_MAX_DIST, NAV_ROW_WORDS = 1, 2, 32766, 8
+NAV_PLAN_KEYS = ("F", "row_words", "field0", "field1", "envs_per_wg", "block", "lds_bytes", "env_bytes")
 
 
 def entity_layout(kz, kp):
@@ -246,6 +249,10 @@ ABI = {
     "zs_entity_obs_layout": [_vp, _i32, _i32, _pi32],
     "zs_entity_obs": [_vp, _vp, _i32, _i32, _vp, _vp],
     "zs_entity_obs_bind": [_vp, _vp, _i32, _i32],
+    "zs_nav_plan": [_vp, _i32, _pi32],
+    "zs_nav_obs": [_vp, _vp, _i32, _i32, _vp, _vp],
+    "zs_nav_field": [_vp, _vp, _i32, _i32, _i32, _vp, _vp],
+    "zs_nav_bind": [_vp, _vp, _i32, _i32],
     "zs_autopilot": [_vp, _vp, _vp, _vp, _vp],
     "zs_autopilot_bind": [_vp, _vp, _vp],
     "zs_env_params_set": [_vp, _vp, _i32, _vp, _vp],

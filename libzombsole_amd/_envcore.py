@@ -174,6 +174,11 @@ class EnvCore(object):
             self._mask_buf = self.torch.zeros((eng.N, eng.A, 8), dtype=self.torch.uint8, device=eng.device)
         return eng.action_mask(out=self._mask_buf)[0, :, :eng.n_discrete].cpu().numpy()
 
+    def path_distances(self, fields=("objective", "zombies"), max_dist=None):
+        """The env's path-distance rows (libzombsole_amd/nav.py), int16 [A, F, 8] on the host: the standalone launch
+        (zs_nav_obs) and a copy, next to action_masks()."""
+        return self.engine.nav_obs(fields=fields, max_dist=max_dist)[0].cpu().numpy()
+
     def scripted_triples(self, policy):
         """The env's scripted action triples under `policy` (a name, a code, or a code per agent), int32 [A, 3] on the
         host: the standalone autopilot launch (zs_autopilot) and a copy, next to action_masks().  Rows of code 0 are

@@ -6,7 +6,8 @@
 // in LDS), k_respawn (deferred zombie respawns, one wave per env) and the observation kernel (zs_obs.hpp: k_obs_ring /
 // k_obs_pipe persistent store streams, k_obs_gather for large maps, k_obs in general), else k_tail, then k_action_mask
 // (zs_mask.hpp) when a mask buffer is bound and k_entity_obs (k_entity_obs.hip, zs_entity_obs.hpp) when an entity
-// buffer is, then k_autopilot (k_autopilot.hip, zs_autopilot.hpp) when a policy is bound.  With a null obs_dev no grid
+// buffer is, then k_nav (k_nav.hip, zs_nav.hpp) when a path-distance buffer is, then k_autopilot (k_autopilot.hip,
+// zs_autopilot.hpp) when a policy is bound.  With a null obs_dev no grid
 // observation is written and k_tail ends the step.  zs_step_graph replays a step as a hipGraph.  The small helpers behind the
 // ABI (seeding, the policy stream, the state views, the drop-ins' per-call records) are k_state.hip's; the per-env
 // record movers (observation-state records, zs_obs_state.hpp; snapshot records, zs_snapshot.hpp and zs_record.hpp) are
@@ -114,6 +115,11 @@ struct zs_handle {
     int32_t* d_obj_xy = nullptr;
     void* ent_bound = nullptr;
     int ent_kz = 0, ent_kp = 0;
+    // path-distance fields (zs_nav.hpp): the launch plan of the handle's map, and zs_nav_bind's buffer, fields and cap
+    // (every zs_step ends with a launch into it)
+    NavPlan nav{};
+    void* nav_bound = nullptr;
+    int nav_fields = 0, nav_max_dist = 0;
     // zs_autopilot_bind: every zs_step ends with an autopilot launch of this policy (uint8 [N][A]) into these triples
     const uint8_t* pilot_policy = nullptr;
     int32_t* pilot_out = nullptr;
@@ -408,6 +414,7 @@ static int create_static_tables(zs_handle* h, const zs_config* cfg, bool* rank_o
     TRY(dupload(h, &d.pspawn, ps));
     TRY(dupload(h, &d.zspawn, zs));
     TRY(dupload(h, &h->d_obj_xy, packlist(m.objective_xy, m.n_objectives)));
+    h->nav = nav_plan(d.W, d.H, d.A);
     TRY(dupload(h, &d.agent_weapons, aw));
     TRY(dupload(h, &d.agent_codes, ac));
     TRY(dupload(h, &d.bot_types, bt));
@@ -877,6 +884,11 @@ extern "C" int zs_step(zs_handle* h, const int32_t* actions_dev, void* obs_dev, 
         const EntityArgs g = {h->ent_kz, h->ent_kp, d.nobj, h->d_obj_xy};
         LAUNCHCHK("k_entity_obs", launch_entity_obs(s, d, g, nullptr, h->ent_bound));
     }
+    //    ... and a bound path-distance buffer (zs_nav_bind), of the same world
+    if (h->nav_bound) {
+        const NavArgs g = {h->nav_fields, h->nav_max_dist, d.nobj, h->d_obj_xy, h->nav};
+        LAUNCHCHK("k_nav", launch_nav(s, d, g, nullptr, h->nav_bound));
+    }
     //    ... and a bound autopilot (zs_autopilot_bind): the scripted triples of that world.  Bound to the caller's action
     //    buffer this is the closed loop: the rows the next step's tick reads
     if (h->pilot_out) LAUNCHCHK("k_autopilot", launch_autopilot(s, d, nullptr, h->pilot_policy, h->pilot_out));
@@ -963,6 +975,73 @@ extern "C" int zs_entity_obs_bind(zs_handle* h, void* out_dev_or_null, int32_t k
     h->ent_bound = out_dev_or_null;
     h->ent_kz = kz;
     h->ent_kp = kp;
+    return ZS_OK;
+}
+
+// the arguments every path-distance call checks before it launches: the fields (rows: a mask; a frame: one bit), the
+// cap, the buffer's alignment, and the plan of the handle's map
+static int nav_args_ok(const zs_handle* h, const void* out_dev, int fields, bool one_field, int max_dist, unsigned align) {
+    if (one_field ? !nav_field_ok(fields) : !nav_fields_ok(fields))
+        return fail(ZS_EINVAL, one_field ? "path distances: field must be ZS_NAV_OBJECTIVE or ZS_NAV_ZOMBIES"
+                                         : "path distances: fields must be a non-empty mask of ZS_NAV_OBJECTIVE | ZS_NAV_ZOMBIES");
+    if (!nav_max_dist_ok(max_dist)) return fail(ZS_EINVAL, "path distances: max_dist must be in 1..32766");
+    if (((uintptr_t)out_dev & (align - 1)) != 0)
+        return fail(ZS_EINVAL, "the path-distance buffer must be " + std::to_string(align) + "-byte aligned");
+    if (!h->nav.ok)
+        return fail(ZS_EINVAL, "path distances: one env's search image (28 * H * ceil(W / 32) + 40 * agents bytes) is past the " +
+                                   std::to_string(ZS_NAV_LDS_LIMIT) + "-byte LDS limit of a workgroup");
+    return ZS_OK;
+}
+
+extern "C" int zs_nav_plan(const zs_handle* h, int32_t fields, int32_t out[8]) {
+    if (!h || !out) return fail(ZS_EINVAL, "null argument");
+    if (!nav_fields_ok(fields))
+        return fail(ZS_EINVAL, "path distances: fields must be a non-empty mask of ZS_NAV_OBJECTIVE | ZS_NAV_ZOMBIES");
+    const int F = nav_nfields(fields);
+    const NavPlan& p = h->nav;
+    const int64_t bytes = nav_env_bytes(h->d.W, h->d.H, h->d.A);
+    const int32_t v[8] = {F, ZS_NAV_ROW_WORDS, 0, F == 2 ? ZS_NAV_ROW_WORDS : -1, p.envs_per_wg, p.block, p.lds_bytes,
+                          (int32_t)std::min<int64_t>(bytes, 0x7fffffff)};
+    std::memcpy(out, v, sizeof(v));
+    return ZS_OK;
+}
+
+// Path-distance rows of the current state (zs_nav.hpp), int16 [N][A][F][8].  Viewer handles included: the kernel reads
+// what zs_obs_state_unpack fills (pos, present, obstacle presence) and the static tables.
+extern "C" int zs_nav_obs(zs_handle* h, const uint8_t* env_mask_dev, int32_t fields, int32_t max_dist, void* out_dev, void* stream) {
+    if (!h || !out_dev) return fail(ZS_EINVAL, "null argument");
+    TRY(nav_args_ok(h, out_dev, fields, false, max_dist, 8));
+    ENTER(h, stream, s);
+    const NavArgs g = {fields, max_dist, h->d.nobj, h->d_obj_xy, h->nav};
+    LAUNCHCHK("k_nav", launch_nav(s, h->d, g, env_mask_dev, out_dev));
+    return ZS_OK;
+}
+
+// The full field of a list of envs, uint16 [n][H][W] (index handling as zs_render's)
+extern "C" int zs_nav_field(zs_handle* h, const int32_t* env_idx_dev, int32_t n, int32_t field, int32_t max_dist, void* out_dev,
+                            void* stream) {
+    if (!h || !out_dev) return fail(ZS_EINVAL, "null argument");
+    if (n < 0) return fail(ZS_EINVAL, "path distances: n must be >= 0");
+    TRY(nav_args_ok(h, out_dev, field, true, max_dist, 2));
+    ENTER(h, stream, s);
+    const NavArgs g = {field, max_dist, h->d.nobj, h->d_obj_xy, h->nav};
+    LAUNCHCHK("k_nav", launch_nav_field(s, h->d, g, env_idx_dev, n, out_dev));
+    return ZS_OK;
+}
+
+extern "C" int zs_nav_bind(zs_handle* h, void* out_dev_or_null, int32_t fields, int32_t max_dist) {
+    if (!h) return fail(ZS_EINVAL, "null handle");
+    NOT_ON_VIEWER(h, "zs_nav_bind");
+    if (out_dev_or_null) {
+        TRY(nav_args_ok(h, out_dev_or_null, fields, false, max_dist, 8));
+    } else {
+        fields = max_dist = 0;
+    }
+    if (out_dev_or_null == h->nav_bound && fields == h->nav_fields && max_dist == h->nav_max_dist) return ZS_OK;
+    TRY(drop_step_graphs(h));
+    h->nav_bound = out_dev_or_null;
+    h->nav_fields = fields;
+    h->nav_max_dist = max_dist;
     return ZS_OK;
 }
 
@@ -1437,14 +1516,16 @@ extern "C" int zs_describe(zs_handle* h, char* buf, int32_t len) {
              "\"mask_grid\": %u, \"mask_block\": %d, \"mask_bound\": %d, \"env_params\": %d, \"episode_stats\": %d, "
              "\"render\": %d, \"render_grid\": %d, \"render_block\": %d, \"entity_obs_bound\": %d, \"entity_kz\": %d, "
              "\"entity_kp\": %d, \"autopilot_kernel\": \"k_autopilot\", \"autopilot_grid\": %u, \"autopilot_block\": %d, "
-             "\"autopilot_bound\": %d, \"step_tail_launch\": \"%s\"}",
+             "\"autopilot_bound\": %d, \"nav_bound\": %d, \"nav_fields\": %d, \"nav_max_dist\": %d, \"nav_kernel\": \"k_nav\", "
+             "\"nav_envs_per_wg\": %d, \"nav_block\": %d, \"nav_lds_bytes\": %d, \"step_tail_launch\": \"%s\"}",
              d.N, d.E, p.G, p.fused ? "k_step" : "k_tick", p.lds, p.resident, p.rw_cap,
              d.fobs ? "step launch" : obs_kernel_name(kf.kind), h->reset_side,
              p.reset_lds, p.defer_respawn ? "k_respawn" : "tick", p.tick_waves, p.rw_step,
              d.par_exec, obs_kernel_name(h->obs.masked.kind), obs_encoders_name(kf), zs_mask_grid(d.N), ZS_MASK_BLOCK,
              h->mask_bound ? 1 : 0, (d.flags & ZS_FLAG_ENV_PARAMS) ? 1 : 0, h->ep.run ? 1 : 0, h->rn.body_col ? 1 : 0,
              h->rn.body_col ? h->rn.plan.bands : 0, h->rn.body_col ? ZS_RENDER_BLOCK : 0,
-             h->ent_bound ? 1 : 0, h->ent_kz, h->ent_kp, zs_pilot_grid(d.N), ZS_PILOT_BLOCK, h->pilot_out ? 1 : 0, h->step_last);
+             h->ent_bound ? 1 : 0, h->ent_kz, h->ent_kp, zs_pilot_grid(d.N), ZS_PILOT_BLOCK, h->pilot_out ? 1 : 0,
+             h->nav_bound ? 1 : 0, h->nav_fields, h->nav_max_dist, h->nav.envs_per_wg, h->nav.block, h->nav.lds_bytes, h->step_last);
     return ZS_OK;
 }
 

@@ -6,6 +6,7 @@
 //   k_reset.hip   k_reset, k_respawn, k_list_filter
 //   k_mask.hip    k_action_mask (zs_mask.hpp)
 //   k_autopilot.hip  k_autopilot (zs_autopilot.hpp, with its launcher's declaration)
+//   k_nav.hip     k_nav (zs_nav.hpp): path-distance fields
 //   k_env_params.hip  k_env_params, k_env_params_get, k_env_params_init, k_env_params_check (ZS_FLAG_ENV_PARAMS)
 //   k_episode.hip  k_episode_stats, k_episode_get, k_episode_clear (ZS_FLAG_EPISODE_STATS; zs_episode.hpp)
 //   k_render.hip  k_render, k_render_track (ZS_FLAG_RENDER; zs_render.hpp)
@@ -19,6 +20,7 @@
 #pragma once
 #include "zs_device.hpp"
 #include "zs_render.hpp"  // RenderPlan, RenderAtlas
+#include "zs_nav.hpp"     // NavArgs, NavPlan
 
 struct ObsStateLayout;  // zs_obs_state.hpp
 struct RecTable;        // zs_record.hpp
@@ -83,6 +85,12 @@ hipError_t stamps_reset(unsigned long long* wg, int clear);
 // action masks (zs_mask.hpp): uint8 [N][A][8] into out, 8-byte aligned, for the envs whose env_mask byte is
 // nonzero (null: all)
 hipError_t launch_action_mask(hipStream_t s, const Dev& d, const uint8_t* env_mask, void* out);
+
+// path-distance fields (k_nav.hip; zs_nav.hpp).  launch_nav: the rows int16 [N][A][F][8] of the envs whose env_mask byte
+// is nonzero (null: all) into out, 8-byte aligned.  launch_nav_field: frame k < n (uint16 [H][W]) of env env_idx[k]
+// (null: k) and the one field g.fields into out + k * W * H; an env outside [0, N) leaves its frame untouched
+hipError_t launch_nav(hipStream_t s, const Dev& d, const NavArgs& g, const uint8_t* env_mask, void* out);
+hipError_t launch_nav_field(hipStream_t s, const Dev& d, const NavArgs& g, const int32_t* env_idx, int n, void* out);
 
 // per-env zombie counts and time limits (k_env_params.hip; ZS_FLAG_ENV_PARAMS handles): entry k
 // < n of params ([n][3]) into the next triple of env idx[k] (null: k), two launches (owner: int32 [N] scratch, -1

@@ -173,6 +173,8 @@ class Engine(object):
         self.masks = None  # the bound action-mask tensor (bind_action_masks), uint8 [N, A, 8]
         self.entities = None  # the bound entity-observation tensor (bind_entity_obs), int16 [N, A, ROW]
         self.entity_k = None  # its (kz, kp)
+        self.nav = None  # the bound path-distance rows (nav_bind), int16 [N, A, F, 8]
+        self.nav_args = None  # its (fields mask, max_dist)
         self.pilot = None  # the bound scripted triples (bind_autopilot), int32 [N, A, 3]; self.actions when bound into it
         self.pilot_policy = None  # the bound policy codes, uint8 [N, A]
 
@@ -343,6 +345,86 @@ class Engine(object):
         self._call("zs_entity_obs_bind", _ptr(buf), int(kz) if buf is not None else 0, int(kp) if buf is not None else 0)
         self.entities = buf
         self.entity_k = (int(kz), int(kp)) if buf is not None else None
+        return buf
+
+    # -- path-distance fields (zs_nav*): walking distance to the objectives and to the zombies, int16 [N, A, F, 8] rows
+    # and uint16 [n, H, W] frames (libzombsole_amd/nav.py) ---------------------------------------------------------
+    def _nav_args(self, fields, max_dist):
+        from . import nav
+        if fields is None and max_dist is None and self.nav_args is not None:
+            return self.nav_args
+        if fields is None:
+            raise ValueError("path distances: fields are needed (no tensor is bound)")
+        return nav.fields_mask(fields), nav._check_max_dist(_abi.NAV_MAX_DIST if max_dist is None else max_dist)
+
+    def nav_layout(self, fields=None):
+        """zs_nav_plan as a dict of _abi.NAV_PLAN_KEYS: "F", "row_words" (8), the word offsets "field0" and "field1" of
+        the fields' rows in an agent's block (-1: not emitted), and the launch plan "envs_per_wg", "block", "lds_bytes"
+        (0 where the map is past the plan's limit) with "env_bytes", one env's search image; with "fields"."""
+        fields = self._nav_args(fields, None)[0] if fields is not None or self.nav_args else _abi.NAV_OBJECTIVE | _abi.NAV_ZOMBIES
+        if ("zs_nav_plan", fields) not in self._layouts:
+            out = (C.c_int32 * len(_abi.NAV_PLAN_KEYS))()
+            self._call("zs_nav_plan", fields, out)
+            self._layouts[("zs_nav_plan", fields)] = dict(zip(_abi.NAV_PLAN_KEYS, (int(v) for v in out)), fields=fields)
+        return dict(self._layouts[("zs_nav_plan", fields)])
+
+    def _check_nav(self, t, fields, what):
+        F = bin(fields).count("1")
+        check_tensor(t, what + ": path distances", self.torch.int16, self.device, self.N, (self.A, F, _abi.NAV_ROW_WORDS), align=8)
+
+    def nav_obs(self, mask=None, out=None, fields=None, max_dist=None):
+        """The path-distance rows of the current state, int16 [N, A, F, 8] (zs_nav_obs; the row: libzombsole_amd/nav.py).
+        `fields`: a bitmask, a name or names ("objective", "zombies"); default: the bound tensor's, with its max_dist.
+        Envs where the uint8 device tensor `mask` is zero keep their bytes.  Into `out` when given, else into the bound
+        tensor (same fields and cap), else into a tensor this call allocates (zeroed)."""
+        fields, max_dist = self._nav_args(fields, max_dist)
+        o = out
+        if o is None and self.nav is not None and (fields, max_dist) == self.nav_args:
+            o = self.nav
+        if o is None:
+            o = self.torch.zeros((self.N, self.A, bin(fields).count("1"), _abi.NAV_ROW_WORDS), dtype=self.torch.int16,
+                                 device=self.device)
+        self._check_nav(o, fields, "nav_obs")
+        self._call("zs_nav_obs", _ptr(mask), fields, max_dist, _ptr(o), self._stream())
+        return o
+
+    def nav_field(self, which, envs=None, out=None, max_dist=None):
+        """The full field `which` ("objective", "zombies" or its bit) of `envs` (an integer tensor or sequence, repeats
+        allowed; default every env in order) as uint16 [n, H, W] on the device, 0xFFFF = unreachable or blocked
+        (zs_nav_field: one launch, no synchronisation).  An index outside [0, N) leaves its frame as it is (0xFFFF in a
+        tensor this call allocates)."""
+        from . import nav
+        t = self.torch
+        which = nav.fields_mask(which)
+        max_dist = nav._check_max_dist(_abi.NAV_MAX_DIST if max_dist is None else max_dist)
+        envs = as_index(t, envs, self.device, "nav_field: envs")
+        n = self.N if envs is None else int(envs.numel())
+        W, H = self.builder.map.size
+        if out is None:
+            out = t.full((n, H, W), -1, dtype=t.int16, device=self.device).view(t.uint16)  # 0xFFFF
+        check_tensor(out, "nav_field: out", t.uint16, self.device, n, (H, W), at_least=True)
+        if n == 0:
+            return out
+        self._call("zs_nav_field", _ptr(envs), n, which, max_dist, _ptr(out), self._stream())
+        return out
+
+    def nav_bind(self, buf=True, fields=("objective", "zombies"), max_dist=None):
+        """Bind `buf` (True: a new tensor; None / False: unbind) so that every step(), step_graph() and step_graphed()
+        ends with a path-distance launch into it (zs_nav_bind); self.nav is the bound tensor and self.nav_args its
+        (fields mask, max_dist)."""
+        t = self.torch
+        if buf is False:
+            buf = None
+        if buf is None:
+            self._call("zs_nav_bind", None, 0, 0)
+            self.nav = self.nav_args = None
+            return None
+        fields, max_dist = self._nav_args(fields, max_dist)
+        if buf is True:
+            buf = t.zeros((self.N, self.A, bin(fields).count("1"), _abi.NAV_ROW_WORDS), dtype=t.int16, device=self.device)
+        self._check_nav(buf, fields, "nav_bind")
+        self._call("zs_nav_bind", _ptr(buf), fields, max_dist)
+        self.nav, self.nav_args = buf, (fields, max_dist)
         return buf
 
     # -- scripted policies for agent slots (zs_autopilot*): the bots' decisions as agent triples, int32 [N, A, 3] -------

@@ -110,6 +110,11 @@ class MultiagentZombsoleEnv(object):
         rows = self._core.scripted_triples(policy)
         return {aid: to_action_dict(rows[i]) for i, aid in enumerate(self._ids)}
 
+    def path_distances(self, fields=("objective", "zombies"), max_dist=None):
+        """Not in the reference: int16 [A, F, 8], every possible agent's path-distance rows on the current world, in the
+        order of the agent ids (libzombsole_amd/nav.py; include/zombsole_mi355x.h, zs_nav_obs)."""
+        return self._core.path_distances(fields, max_dist)
+
     def _process_single_agent_action(self, sp_action):
         coords = sp_action.get("parameter", [0, 0])
         return {"action_type": sp_action["action_type"], "parameter": coords}
@@ -191,6 +196,9 @@ class MultiAgentWrapper(object):
 
     def scripted_actions(self, policy="terminator"):
         return self.env.scripted_actions(policy)
+
+    def path_distances(self, fields=("objective", "zombies"), max_dist=None):
+        return self.env.path_distances(fields, max_dist)
 
     def close(self):
         self.env.close()

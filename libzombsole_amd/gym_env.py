@@ -88,6 +88,11 @@ class ZombsoleGymEnv(Env):
         from .autopilot import to_action_dict
         return to_action_dict(self._core.scripted_triples(policy)[0])
 
+    def path_distances(self, fields=("objective", "zombies"), max_dist=None):
+        """Not in the reference: int16 [F, 8], the agent's path-distance rows on the current world
+        (libzombsole_amd/nav.py; include/zombsole_mi355x.h, zs_nav_obs)."""
+        return self._core.path_distances(fields, max_dist)[0]
+
     def step(self, action):
         """gym_env.py:99-145: set_action, World.step, reward, respawn, obs, rules, end reward."""
         self.game.agents[0].set_action(action)

@@ -68,7 +68,7 @@ class BatchedZombsole(object):
                  observation_surroundings_width=21, observation_position_encoding_style="channels",
                  agent_weapons="rifle", obs_dtype=None, autoreset=True, device=None, lanes_per_env=0,
                  action_masks=False, env_params=False, episode_stats=False, render=False, entity_obs=None,
-                 grid_obs=True, autopilot=None, autopilot_into_actions=False):
+                 grid_obs=True, autopilot=None, autopilot_into_actions=False, nav=None, nav_max_dist=32766):
         if surface == "single":
             b = _abi.single_env_config(num_envs, rules_name, player_names, map_name, agent_id, initial_zombies,
                                        minimum_zombies, observation_scope, observation_position_encoding,
@@ -102,6 +102,10 @@ class BatchedZombsole(object):
         # grid_obs=False: no grid observation is allocated or written; the entity tensor is the observation
         if entity_obs is not None:
             self.engine.bind_entity_obs(True, int(entity_obs[0]), int(entity_obs[1]))
+        # nav=("objective", "zombies") | "objective" | "zombies": path-distance rows (libzombsole_amd/nav.py) bound the
+        # same way, refreshed at the same places
+        if nav is not None:
+            self.engine.nav_bind(True, nav, nav_max_dist)
         # autopilot="terminator" | "sniper" | "troll" | uint8 [N, A] codes: scripted triples bound the same way
         # (libzombsole_amd/autopilot.py), refreshed at the same places.  autopilot_into_actions=True binds the engine's
         # action buffer: a step's last launch writes the rows the next step reads
@@ -139,8 +143,22 @@ class BatchedZombsole(object):
             eng.action_mask(mask)
         if eng.entities is not None:
             eng.entity_obs(mask)
+        if eng.nav is not None:
+            eng.nav_obs(mask)
         if eng.pilot is not None:
             eng.autopilot(eng.pilot_policy, mask, out=eng.pilot)
+
+    @property
+    def nav_obs(self):
+        """int16 [N, A, F, 8]: the engine's bound path-distance rows (libzombsole_amd/nav.py) of the world self.obs shows.
+        Valid after every reset, step, restore / clone and load_checkpoint.  None without nav=."""
+        return self.engine.nav
+
+    def nav_field(self, which, envs=None, out=None):
+        """Engine.nav_field with the bound cap: the full field `which` of `envs` (default: all), uint16 [n, H, W] on the
+        device, 0xFFFF = unreachable or blocked."""
+        args = self.engine.nav_args
+        return self.engine.nav_field(which, envs, out, max_dist=args[1] if args else None)
 
     @property
     def entity_obs(self):
@@ -271,7 +289,8 @@ class BatchedZombsole(object):
         grid_obs=False: the entity tensor, which is refreshed whenever one is bound)."""
         eng, t = self.engine, self.torch
         eng.restore(snap, src, dst, check=check)
-        if not observe and self.engine.masks is None and self.engine.entities is None and self.engine.pilot is None:
+        if (not observe and self.engine.masks is None and self.engine.entities is None and self.engine.pilot is None and
+                self.engine.nav is None):
             return None
         mask = t.zeros(eng.N, dtype=t.uint8, device=eng.device)
         if dst is None:
