@@ -33,6 +33,23 @@
  * state; the caller owns every output buffer.  All calls on one handle are
  * serialized on the stream they are given.  Return value 0 = ok, otherwise a
  * ZS_E* code with a message in zs_last_error() (thread-local).
+ *
+ * Streams.  Every launch, copy and memset of a call goes to the `stream` it is given (the next-step reset
+ * work of zs_step may run on a stream of the handle's own, forked from `stream` and joined to it inside the
+ * call).  A call that takes device buffers only returns without waiting for the device: zs_observe, zs_step,
+ * zs_gen_actions, zs_obs_state_pack / _unpack, zs_snapshot, zs_restore, zs_action_mask, zs_entity_obs,
+ * zs_nav_obs, zs_nav_field, zs_autopilot, zs_env_params_set / _get, zs_episode_stats_get / _clear, zs_render.
+ * A call that hands a host value back, or reads a host buffer, waits for `stream` (and for nothing else)
+ * before it returns: zs_seed, zs_reset (its error word), zs_get_state / zs_set_state, zs_get_rng / zs_set_rng,
+ * zs_overflow, zs_env_params_check, zs_debug_lists, zs_death_log, zs_action_log and the zs_host_* calls.
+ * zs_step_graph(_n) waits for `stream` in the call that captures a buffer set, and only launches the graph
+ * when it finds the set cached.  The calls without a stream that change what a step launches wait for the
+ * whole device: the zs_*_bind calls when the binding changes (none when it is the one in place) and
+ * zs_render_sprites; zs_profile_read waits for its own events.
+ * The handle's scratch (the state and seed staging rows, the error word, zs_env_params_set's row, the step
+ * counter of zs_step_graph) is shared by all its calls: a caller that moves to another stream orders that
+ * stream after the previous call with an event of its own, and two calls of one handle in flight on streams
+ * that are not ordered are not supported.
  */
 #ifndef ZOMBSOLE_MI355X_H
 #define ZOMBSOLE_MI355X_H
@@ -291,6 +308,12 @@ int zs_gen_actions(zs_handle* h, uint64_t step, int32_t n_discrete, int32_t* act
  * one per call on the device.  The launches are captured once per pending-reset-list parity for
  * each set of buffer arguments (the last 4 sets are kept, so double-buffered outputs replay
  * without recapture); results equal zs_gen_actions + zs_step.
+ * The step counter is one per handle, shared by all its cached sets: a call that captures a set with a policy
+ * (a new key, an evicted one, any key after a zs_*_bind change) writes step0 into it; a call that finds its
+ * set cached ignores step0 and plays the counter's step, which every policy step of a graph advances by one.
+ * zs_step, and graphs with n_discrete = 0 (captured or replayed), neither read nor move the counter: after k
+ * such steps a cached policy graph continues k steps behind the episode's step number.  A caller that mixes
+ * them and needs the true step number plays those steps through a policy graph too, or forces a recapture.
  * n_discrete = 0: no policy.  The graph replays zs_step on the caller's actions_dev, which the
  * caller fills on `stream` before each call (a learner's actions, derived from the previous step's
  * observations); results equal zs_step.  This is the graphed form of the reference's per-tick

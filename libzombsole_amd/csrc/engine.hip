@@ -1120,8 +1120,10 @@ extern "C" int zs_step_graph_n(zs_handle* h, uint64_t step0, int32_t n_discrete,
         if (!h->d_gstep) {
             TRY(dalloc(h, &h->d_gstep, 2));
         }
+        // the policy step counter is the policy graphs' alone: a set without a policy (n_discrete = 0) neither reads
+        // nor advances it, so capturing one in mid-run leaves it where the policy graphs continue from
         uint64_t init[2] = {step0, 0};
-        HIPCHK(hipMemcpyAsync(h->d_gstep, init, sizeof(init), hipMemcpyHostToDevice, s));
+        if (n_discrete > 0) HIPCHK(hipMemcpyAsync(h->d_gstep, init, sizeof(init), hipMemcpyHostToDevice, s));
         HIPCHK(hipStreamSynchronize(s));
         hipStream_t cs;
         HIPCHK(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));

@@ -236,8 +236,9 @@ class Engine(object):
         return None if o.obs is None else o.obs[:self.N]
 
     def step_graph(self, step0, n_discrete, out=None, steps=1, actions=None):
-        """gen_actions(t, n_discrete) + step() as one replayed hipGraph (t = step0 on the first call,
-        then advancing by one per step on the device).  steps > 1: that many steps per graph launch
+        """gen_actions(t, n_discrete) + step() as one replayed hipGraph (t = step0 on the call that captures the
+        buffer set, then advancing by one per policy step on the device: a cached set ignores step0, and step(),
+        step_graphed() and other n_discrete = 0 graphs do not move the counter).  steps > 1: that many steps per graph launch
         (zs_step_graph_n), the outputs holding the last one's.  n_discrete = 0: no policy, the graph
         replays step(actions) on the caller's action tensor (default self.actions), which the caller
         fills on the current stream before each call (see step_graphed)."""
