@@ -38,7 +38,7 @@
  * work of zs_step may run on a stream of the handle's own, forked from `stream` and joined to it inside the
  * call).  A call that takes device buffers only returns without waiting for the device: zs_observe, zs_step,
  * zs_gen_actions, zs_obs_state_pack / _unpack, zs_snapshot, zs_restore, zs_action_mask, zs_entity_obs,
- * zs_nav_obs, zs_nav_field, zs_autopilot, zs_env_params_set / _get, zs_episode_stats_get / _clear, zs_render.
+ * zs_entity_act_decode / _mask / _encode, zs_nav_obs, zs_nav_field, zs_autopilot, zs_env_params_set / _get, zs_episode_stats_get / _clear, zs_render.
  * A call that hands a host value back, or reads a host buffer, waits for `stream` (and for nothing else)
  * before it returns: zs_seed, zs_reset (its error word), zs_get_state / zs_set_state, zs_get_rng / zs_set_rng,
  * zs_overflow, zs_env_params_check, zs_debug_lists, zs_death_log, zs_action_log and the zs_host_* calls.
@@ -488,6 +488,61 @@ int zs_entity_obs_layout(const zs_handle* h, int32_t kz, int32_t kp, int32_t out
 int zs_entity_obs(zs_handle* h, const uint8_t* env_mask_dev, int32_t kz, int32_t kp, void* out_dev, void* stream);
 int zs_entity_obs_bind(zs_handle* h, void* out_dev_or_null, int32_t kz, int32_t kp);
 
+/* ---- entity-targeted actions: a pointer action table over the entity observation's rows ---------------------
+ * NID = 15 + kz + kp ids per agent, kz and kp those of the entity observation (1 <= kz <= 16, 0 <= kp <= 16, else
+ * ZS_EINVAL before any launch).  Everything is evaluated on the env's current world, the one its observation shows (an
+ * env pending its reset: the terminal world).  dir k = (0,1), (-1,0), (0,-1), (1,0).
+ *   id                   triple                                  mask bit is 1 exactly when
+ *   0..3                 (ZS_ACT_MOVE, dir k)                    as zs_action_mask byte k
+ *   4                    (ZS_ACT_ATTACK_CLOSEST, 0, 0)           as zs_action_mask byte 4
+ *   5                    (ZS_ACT_HEAL, 0, 0)                     1
+ *   6                    (ZS_ACT_HEAL_CLOSEST, 0, 0)             zs_action_mask byte 6 by the multi surface's rule, on both
+ *                                                                surfaces (Agent.next_step takes heal_closest on either)
+ *   7..10                (ZS_ACT_ATTACK, dir k)                  the adjacent cell is inside the map and World.things holds a
+ *                                                                thing there: a present obstacle whatever its life, or a
+ *                                                                present zombie, bot or agent (every weapon reaches distance 1)
+ *   11..14               (ZS_ACT_HEAL, dir k)                    the adjacent cell holds a present agent or bot or a present
+ *                                                                obstacle, not a zombie (players/agent.py:69-75)
+ *   15 + j, j < kz       (ZS_ACT_ATTACK, dx_j, dy_j)             zombie row j of the entity observation is valid and its
+ *                                                                d2 <= weapon_r2 (the row's bit 1)
+ *   15 + kz + j, j < kp  (ZS_ACT_HEAL, dx_j, dy_j)               player row j is valid and its d2 <= 9 (the row's bit 1)
+ * Row j is the j-th present zombie, or the j-th other present agent or bot, ascending by (d2, slot): the entity
+ * observation's order.  A mask bit means what zs_action_mask's bytes mean: were this the agent's action and the first
+ * one executed, Agent.next_step would return an action and World.thing_move / thing_attack / thing_heal would log 'moved
+ * to', 'injured' or 'healed'.  Friendly fire is an action the reference carries out, so its bit is 1.
+ * Decode: a valid row decodes to its triple whether or not the mask allows it (the tick then reports 'too far', as the
+ * reference does); an id whose row is not valid decodes to (ZS_ACT_IDLE, 0, 0); an id outside [0, NID) does too and
+ * raises the sticky ZS_OVF_PARAM_RANGE bit of zs_overflow's word; an agent that is not in the world gets (ZS_ACT_IDLE,
+ * 0, 0) and an all-zero mask row.
+ * Encode: the smallest id of [0, NID) whose decoded triple equals the given triple word for word on the current world,
+ * else -1.  Every triple zs_autopilot writes has an id.
+ *
+ * zs_entity_act_table: out[0] = NID, out[1] = the mask row's bytes (NID rounded up to 8; padding bytes are 0), out[2..6]
+ * = the first id of the blocks attack-dir (7), heal-dir (11), zombie rows (15), player rows (15 + kz), end (NID),
+ * out[7] = 0.
+ * zs_entity_act_decode: ids_dev int32 [N][num_agents] into actions_dev int32 [N][num_agents][3].
+ * zs_entity_act_mask: mask_dev uint8 [N][num_agents][row bytes], 8-byte aligned (else ZS_EINVAL).
+ * zs_entity_act_encode: triples_dev int32 [N][num_agents][3] into ids_out_dev int32 [N][num_agents].
+ * All three: one launch on `hip_stream` (a hipStream_t passed as void*, what the other calls name `stream`), no host
+ * synchronisation; envs whose env_mask_dev byte is 0 are untouched (NULL = all).  Any handle: a viewer's envs
+ * (zs_obs_state_unpack) hold everything the kernels read, which is what zs_action_mask and zs_entity_obs read.
+ * zs_entity_act_bind: while mask_dev is bound (non-NULL), every zs_step launches the masks of all envs into it after a
+ * bound entity-observation launch and before a bound path-distance launch.  While ids_dev is bound, every zs_step begins
+ * with the decode of all envs from ids_dev into that call's actions_dev, on the caller's stream ahead of the reset
+ * work's fork.  Both hold eagerly, for each step of zs_step_graph(_n) (n_steps > 1: each step decodes the same ids
+ * against its own world) and through zs_host_step.  While ids_dev is bound, zs_step_graph(_n) with n_discrete != 0 is
+ * ZS_EINVAL: the generated policy would overwrite the decoded rows.  Binding other buffers, other K values or NULL drops
+ * the cached graphs; unlike the other *_bind calls this one does not wait for the device: it marks the sets, and the
+ * next zs_step_graph(_n) waits for its stream and destroys them before it captures anew.  A handle that never binds
+ * launches what it did before.  The buffers must outlive the binding.  ZS_ESTATE on a viewer handle. */
+int zs_entity_act_table(const zs_handle* h, int32_t kz, int32_t kp, int32_t out[8]);
+int zs_entity_act_decode(zs_handle* h, const uint8_t* env_mask_dev, int32_t kz, int32_t kp, const int32_t* ids_dev,
+                         int32_t* actions_dev, void* hip_stream);
+int zs_entity_act_mask(zs_handle* h, const uint8_t* env_mask_dev, int32_t kz, int32_t kp, void* mask_dev, void* hip_stream);
+int zs_entity_act_encode(zs_handle* h, const uint8_t* env_mask_dev, int32_t kz, int32_t kp, const int32_t* triples_dev,
+                         int32_t* ids_out_dev, void* hip_stream);
+int zs_entity_act_bind(zs_handle* h, const int32_t* ids_dev_or_null, void* mask_dev_or_null, int32_t kz, int32_t kp);
+
 /* ---- path-distance fields: walking distance to the objectives and to the zombies, per env -------------------
  * A cell is free when it is inside the map and holds no present obstacle, whatever the obstacle's life (the rule of
  * the entity observation's rays); entities never block.  A field is the 4-connected breadth-first distance over free
@@ -695,6 +750,8 @@ int zs_profile_read(zs_handle* h, double out[8]);
  * "autopilot_bound" whether a policy is bound (zs_autopilot_bind); "nav_kernel", "nav_envs_per_wg", "nav_block",
  * "nav_lds_bytes" the path-distance launch (zs_nav_obs; 0 where the map is past its plan's limit), "nav_bound" whether
  * a buffer is bound (zs_nav_bind) and "nav_fields", "nav_max_dist" its arguments (0 when none);
+ * "entity_act_kernel" the entity action table's kernels (zs_entity_act_*), "entity_act_ids_bound" and
+ * "entity_act_mask_bound" whether ids and a mask buffer are bound (zs_entity_act_bind);
  * "step_tail_launch" the launch that carried the tail of the last zs_step queued or captured: the observation kernel,
  * or "k_tail" when the step launch wrote the observations itself or obs_dev was NULL ("" before any step).
  * Returns ZS_OK. */

@@ -139,6 +139,8 @@ LAYOUT_KEYS = {
 }
 
 ENTITY_KMAX, ENTITY_RAY_CAP = 16, 16
+# the entity action table (csrc/zs_entity_act.hpp): the words of zs_entity_act_table's out[] (None: reserved)
+ENTITY_ACT_TABLE_KEYS = ("nid", "row_bytes", "attack_dir", "heal_dir", "zombie_rows", "player_rows", "end", None)
 # path-distance fields (csrc/zs_nav.hpp): the field bits, the largest cap, the words of zs_nav_plan's out[]
 NAV_OBJECTIVE, NAV_ZOMBIES, NAV_MAX_DIST, NAV_ROW_WORDS = 1, 2, 32766, 8
 NAV_PLAN_KEYS = ("F", "row_words", "field0", "field1", "envs_per_wg", "block", "lds_bytes", "env_bytes")
@@ -249,6 +251,11 @@ ABI = {
     "zs_entity_obs_layout": [_vp, _i32, _i32, _pi32],
     "zs_entity_obs": [_vp, _vp, _i32, _i32, _vp, _vp],
     "zs_entity_obs_bind": [_vp, _vp, _i32, _i32],
+    "zs_entity_act_table": [_vp, _i32, _i32, _pi32],
+    "zs_entity_act_decode": [_vp, _vp, _i32, _i32, _vp, _vp, _vp],
+    "zs_entity_act_mask": [_vp, _vp, _i32, _i32, _vp, _vp],
+    "zs_entity_act_encode": [_vp, _vp, _i32, _i32, _vp, _vp, _vp],
+    "zs_entity_act_bind": [_vp, _vp, _vp, _i32, _i32],
     "zs_nav_plan": [_vp, _i32, _pi32],
     "zs_nav_obs": [_vp, _vp, _i32, _i32, _vp, _vp],
     "zs_nav_field": [_vp, _vp, _i32, _i32, _i32, _vp, _vp],

@@ -174,6 +174,18 @@ class EnvCore(object):
             self._mask_buf = self.torch.zeros((eng.N, eng.A, 8), dtype=self.torch.uint8, device=eng.device)
         return eng.action_mask(out=self._mask_buf)[0, :, :eng.n_discrete].cpu().numpy()
 
+    def entity_action_masks(self, kz=4, kp=1):
+        """The env's entity-action masks (libzombsole_amd/entity_act.py), uint8 [A, 15 + kz + kp] on the host: the
+        standalone launch (zs_entity_act_mask) and a copy, next to action_masks()."""
+        nid = self.engine.entity_act_layout(kz, kp)["nid"]
+        return self.engine.entity_act_mask(kz=kz, kp=kp)[0, :, :nid].cpu().numpy()
+
+    def entity_action_triples(self, ids, kz=4, kp=1):
+        """The triples of one entity-action id per agent on the current world, int32 [A, 3] on the host
+        (zs_entity_act_decode)."""
+        eng, t = self.engine, self.torch
+        return eng.entity_act_decode(t.as_tensor(ids, dtype=t.int32).reshape(eng.N, eng.A).to(eng.device), kz=kz, kp=kp)[0].cpu().numpy()
+
     def path_distances(self, fields=("objective", "zombies"), max_dist=None):
         """The env's path-distance rows (libzombsole_amd/nav.py), int16 [A, F, 8] on the host: the standalone launch
         (zs_nav_obs) and a copy, next to action_masks()."""

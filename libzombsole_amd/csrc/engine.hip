@@ -6,7 +6,8 @@
 // in LDS), k_respawn (deferred zombie respawns, one wave per env) and the observation kernel (zs_obs.hpp: k_obs_ring /
 // k_obs_pipe persistent store streams, k_obs_gather for large maps, k_obs in general), else k_tail, then k_action_mask
 // (zs_mask.hpp) when a mask buffer is bound and k_entity_obs (k_entity_obs.hip, zs_entity_obs.hpp) when an entity
-// buffer is, then k_nav (k_nav.hip, zs_nav.hpp) when a path-distance buffer is, then k_autopilot (k_autopilot.hip,
+// buffer is, then k_entity_act_mask (k_entity_act.hip, zs_entity_act.hpp) when an entity-action mask buffer is (bound
+// entity-action ids are decoded into the step's actions by k_entity_act_decode, the step's first launch), then k_nav (k_nav.hip, zs_nav.hpp) when a path-distance buffer is, then k_autopilot (k_autopilot.hip,
 // zs_autopilot.hpp) when a policy is bound.  With a null obs_dev no grid
 // observation is written and k_tail ends the step.  zs_step_graph replays a step as a hipGraph.  The small helpers behind the
 // ABI (seeding, the policy stream, the state views, the drop-ins' per-call records) are k_state.hip's; the per-env
@@ -31,6 +32,7 @@
 #include "zs_record.hpp"
 #include "zs_mask.hpp"  // the mask launch's geometry (zs_describe); the kernel is k_mask.hip's
 #include "zs_entity_obs.hpp"  // the entity observation's layout and launcher; the kernel is k_entity_obs.hip's
+#include "zs_entity_act.hpp"  // the entity action table's layout and launchers; the kernels are k_entity_act.hip's
 #include "zs_autopilot.hpp"  // the scripted policies' launcher and geometry; the kernel is k_autopilot.hip's
 #include "zs_episode.hpp"  // the running part's columns (ZS_EP_RUN_COLS); the kernels are k_episode.hip's
 
@@ -91,6 +93,7 @@ struct zs_handle {
     static const int kGraphSets = 4;
     GraphSet gsets[kGraphSets];
     uint64_t gclock = 0;
+    bool graphs_stale = false;  // zs_entity_act_bind changed what a step launches: the sets are dropped before the next replay
     uint64_t* d_gstep = nullptr;  // [0] policy step counter (the step's policy reads it, the step's tail advances it)
     int graph_pol = 0;            // zs_step_graph is capturing a step with this policy (n_discrete), else 0
     // next-step reset work on a side stream, concurrent with the tick (the two touch disjoint envs);
@@ -115,6 +118,11 @@ struct zs_handle {
     int32_t* d_obj_xy = nullptr;
     void* ent_bound = nullptr;
     int ent_kz = 0, ent_kp = 0;
+    // zs_entity_act_bind: every zs_step begins with the decode of these ids (int32 [N][A]) into its actions, and launches
+    // the table's masks into this buffer after a bound entity-observation launch
+    const int32_t* eact_ids = nullptr;
+    void* eact_mask = nullptr;
+    int eact_kz = 0, eact_kp = 0;
     // path-distance fields (zs_nav.hpp): the launch plan of the handle's map, and zs_nav_bind's buffer, fields and cap
     // (every zs_step ends with a launch into it)
     NavPlan nav{};
@@ -806,6 +814,11 @@ extern "C" int zs_step(zs_handle* h, const int32_t* actions_dev, void* obs_dev, 
     // ZS_FLAG_EPISODE_STATS: the update rule reads the tick's reset flags, so a caller that wants none gets the
     // handle's own row (one row whatever the caller's buffers: the step graphs stay keyed on the caller's pointers)
     if ((h->ep.run || h->rn.body_col) && !reset_dev) reset_dev = h->d_ep_reset;
+    // 0) bound entity-action ids (zs_entity_act_bind): decoded against the world the last observation showed into the
+    //    rows the tick reads, on the caller's stream ahead of the fork, so the side-stream reset work is ordered after it
+    if (h->eact_ids)
+        LAUNCHCHK("k_entity_act_decode",
+                  launch_entity_act_decode(s, h->d, h->eact_kz, h->eact_kp, nullptr, h->eact_ids, const_cast<int32_t*>(actions_dev)));
     // 1) rebuild the envs that ended at the previous call (list[p]); fused into the tick launch
     //    when the LDS images allow, else a k_reset launch first
     int q = 1 - h->rpar, rc = ZS_OK;
@@ -884,6 +897,8 @@ extern "C" int zs_step(zs_handle* h, const int32_t* actions_dev, void* obs_dev, 
         const EntityArgs g = {h->ent_kz, h->ent_kp, d.nobj, h->d_obj_xy};
         LAUNCHCHK("k_entity_obs", launch_entity_obs(s, d, g, nullptr, h->ent_bound));
     }
+    //    ... and a bound entity-action mask buffer (zs_entity_act_bind), of the same world
+    if (h->eact_mask) LAUNCHCHK("k_entity_act_mask", launch_entity_act_mask(s, d, h->eact_kz, h->eact_kp, nullptr, h->eact_mask));
     //    ... and a bound path-distance buffer (zs_nav_bind), of the same world
     if (h->nav_bound) {
         const NavArgs g = {h->nav_fields, h->nav_max_dist, d.nobj, h->d_obj_xy, h->nav};
@@ -975,6 +990,82 @@ extern "C" int zs_entity_obs_bind(zs_handle* h, void* out_dev_or_null, int32_t k
     h->ent_bound = out_dev_or_null;
     h->ent_kz = kz;
     h->ent_kp = kp;
+    return ZS_OK;
+}
+
+static int eact_k_ok(int kz, int kp) {
+    if (!ent_k_ok(kz, kp)) return fail(ZS_EINVAL, "entity actions: kz must be in 1..16 and kp in 0..16");
+    return ZS_OK;
+}
+static int eact_mask_ok(const void* mask_dev) {
+    if (((uintptr_t)mask_dev & 7u) != 0) return fail(ZS_EINVAL, "the entity-action mask buffer must be 8-byte aligned");
+    return ZS_OK;
+}
+static int eact_ids_ok(const void* p) {
+    if (((uintptr_t)p & 3u) != 0) return fail(ZS_EINVAL, "entity-action ids and triples must be 4-byte aligned");
+    return ZS_OK;
+}
+
+extern "C" int zs_entity_act_table(const zs_handle* h, int32_t kz, int32_t kp, int32_t out[8]) {
+    if (!h || !out) return fail(ZS_EINVAL, "null argument");
+    TRY(eact_k_ok(kz, kp));
+    const int32_t v[8] = {eact_nid(kz, kp), eact_row_bytes(kz, kp), ZS_EACT_ATTACK_DIR, ZS_EACT_HEAL_DIR, eact_zombie_id(0),
+                          eact_player_id(kz, 0), eact_nid(kz, kp), 0};
+    std::memcpy(out, v, sizeof(v));
+    return ZS_OK;
+}
+
+// The entity action table on the current state (zs_entity_act.hpp).  Viewer handles included: the kernels read what
+// zs_obs_state_unpack fills (pos, present, weapon, obstacle presence) and the static cell map.
+extern "C" int zs_entity_act_decode(zs_handle* h, const uint8_t* env_mask_dev, int32_t kz, int32_t kp, const int32_t* ids_dev,
+                                    int32_t* actions_dev, void* stream) {
+    if (!h || !ids_dev || !actions_dev) return fail(ZS_EINVAL, "null argument");
+    TRY(eact_k_ok(kz, kp));
+    TRY(eact_ids_ok(ids_dev));
+    TRY(eact_ids_ok(actions_dev));
+    ENTER(h, stream, s);
+    LAUNCHCHK("k_entity_act_decode", launch_entity_act_decode(s, h->d, kz, kp, env_mask_dev, ids_dev, actions_dev));
+    return ZS_OK;
+}
+
+extern "C" int zs_entity_act_mask(zs_handle* h, const uint8_t* env_mask_dev, int32_t kz, int32_t kp, void* mask_dev, void* stream) {
+    if (!h || !mask_dev) return fail(ZS_EINVAL, "null argument");
+    TRY(eact_k_ok(kz, kp));
+    TRY(eact_mask_ok(mask_dev));
+    ENTER(h, stream, s);
+    LAUNCHCHK("k_entity_act_mask", launch_entity_act_mask(s, h->d, kz, kp, env_mask_dev, mask_dev));
+    return ZS_OK;
+}
+
+extern "C" int zs_entity_act_encode(zs_handle* h, const uint8_t* env_mask_dev, int32_t kz, int32_t kp, const int32_t* triples_dev,
+                                    int32_t* ids_out_dev, void* stream) {
+    if (!h || !triples_dev || !ids_out_dev) return fail(ZS_EINVAL, "null argument");
+    TRY(eact_k_ok(kz, kp));
+    TRY(eact_ids_ok(triples_dev));
+    TRY(eact_ids_ok(ids_out_dev));
+    ENTER(h, stream, s);
+    LAUNCHCHK("k_entity_act_encode", launch_entity_act_encode(s, h->d, kz, kp, env_mask_dev, triples_dev, ids_out_dev));
+    return ZS_OK;
+}
+
+extern "C" int zs_entity_act_bind(zs_handle* h, const int32_t* ids_dev_or_null, void* mask_dev_or_null, int32_t kz, int32_t kp) {
+    if (!h) return fail(ZS_EINVAL, "null handle");
+    NOT_ON_VIEWER(h, "zs_entity_act_bind");
+    if (ids_dev_or_null || mask_dev_or_null) {
+        TRY(eact_k_ok(kz, kp));
+        TRY(eact_ids_ok(ids_dev_or_null));
+        TRY(eact_mask_ok(mask_dev_or_null));
+    } else {
+        kz = kp = 0;
+    }
+    if (ids_dev_or_null == h->eact_ids && mask_dev_or_null == h->eact_mask && kz == h->eact_kz && kp == h->eact_kp) return ZS_OK;
+    // the cached step graphs hold the old launch sequence: the next zs_step_graph(_n) drops them behind its stream
+    // (no wait here: an eager step in flight has read its binding when it was queued)
+    h->graphs_stale = true;
+    h->eact_ids = ids_dev_or_null;
+    h->eact_mask = mask_dev_or_null;
+    h->eact_kz = kz;
+    h->eact_kp = kp;
     return ZS_OK;
 }
 
@@ -1103,7 +1194,18 @@ extern "C" int zs_step_graph_n(zs_handle* h, uint64_t step0, int32_t n_discrete,
     // n_discrete = 0: the caller's actions (no policy launch; the graph replays zs_step on actions_dev)
     if (n_discrete < 0 || n_discrete > 7) return fail(ZS_EINVAL, "n_discrete must be in 0..7");
     if (n_steps < 1 || n_steps > 64) return fail(ZS_EINVAL, "n_steps must be in 1..64");
+    if (n_discrete != 0 && h->eact_ids)
+        return fail(ZS_EINVAL, "zs_step_graph: n_discrete must be 0 while entity-action ids are bound (the generated policy "
+                               "would overwrite the decoded rows)");
     ENTER(h, stream, s);
+    if (h->graphs_stale) {  // a binding changed since the sets were captured: wait for the replays queued on s, drop them
+        HIPCHK(hipStreamSynchronize(s));
+        for (auto& gs : h->gsets) {
+            HIPCHK(destroy_graphs(gs));
+            gs.used = 0;
+        }
+        h->graphs_stale = false;
+    }
     const void* key[9] = {actions_dev, obs_dev, rewards_dev, done_dev, trunc_dev, listed_dev, reset_dev,
                           (const void*)(intptr_t)n_discrete, (const void*)(intptr_t)n_steps};
     zs_handle::GraphSet* set = nullptr;
@@ -1519,7 +1621,8 @@ extern "C" int zs_describe(zs_handle* h, char* buf, int32_t len) {
              "\"render\": %d, \"render_grid\": %d, \"render_block\": %d, \"entity_obs_bound\": %d, \"entity_kz\": %d, "
              "\"entity_kp\": %d, \"autopilot_kernel\": \"k_autopilot\", \"autopilot_grid\": %u, \"autopilot_block\": %d, "
              "\"autopilot_bound\": %d, \"nav_bound\": %d, \"nav_fields\": %d, \"nav_max_dist\": %d, \"nav_kernel\": \"k_nav\", "
-             "\"nav_envs_per_wg\": %d, \"nav_block\": %d, \"nav_lds_bytes\": %d, \"step_tail_launch\": \"%s\"}",
+             "\"nav_envs_per_wg\": %d, \"nav_block\": %d, \"nav_lds_bytes\": %d, \"entity_act_kernel\": \"k_entity_act\", "
+             "\"entity_act_ids_bound\": %d, \"entity_act_mask_bound\": %d, \"step_tail_launch\": \"%s\"}",
              d.N, d.E, p.G, p.fused ? "k_step" : "k_tick", p.lds, p.resident, p.rw_cap,
              d.fobs ? "step launch" : obs_kernel_name(kf.kind), h->reset_side,
              p.reset_lds, p.defer_respawn ? "k_respawn" : "tick", p.tick_waves, p.rw_step,
@@ -1527,7 +1630,8 @@ extern "C" int zs_describe(zs_handle* h, char* buf, int32_t len) {
              h->mask_bound ? 1 : 0, (d.flags & ZS_FLAG_ENV_PARAMS) ? 1 : 0, h->ep.run ? 1 : 0, h->rn.body_col ? 1 : 0,
              h->rn.body_col ? h->rn.plan.bands : 0, h->rn.body_col ? ZS_RENDER_BLOCK : 0,
              h->ent_bound ? 1 : 0, h->ent_kz, h->ent_kp, zs_pilot_grid(d.N), ZS_PILOT_BLOCK, h->pilot_out ? 1 : 0,
-             h->nav_bound ? 1 : 0, h->nav_fields, h->nav_max_dist, h->nav.envs_per_wg, h->nav.block, h->nav.lds_bytes, h->step_last);
+             h->nav_bound ? 1 : 0, h->nav_fields, h->nav_max_dist, h->nav.envs_per_wg, h->nav.block, h->nav.lds_bytes,
+             h->eact_ids ? 1 : 0, h->eact_mask ? 1 : 0, h->step_last);
     return ZS_OK;
 }
 

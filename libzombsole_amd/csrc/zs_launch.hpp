@@ -6,6 +6,8 @@
 //   k_reset.hip   k_reset, k_respawn, k_list_filter
 //   k_mask.hip    k_action_mask (zs_mask.hpp)
 //   k_autopilot.hip  k_autopilot (zs_autopilot.hpp, with its launcher's declaration)
+//   k_entity_act.hip  k_entity_act_decode, k_entity_act_mask, k_entity_act_encode (zs_entity_act.hpp, with their launchers'
+//                     declarations)
 //   k_nav.hip     k_nav (zs_nav.hpp): path-distance fields
 //   k_env_params.hip  k_env_params, k_env_params_get, k_env_params_init, k_env_params_check (ZS_FLAG_ENV_PARAMS)
 //   k_episode.hip  k_episode_stats, k_episode_get, k_episode_clear (ZS_FLAG_EPISODE_STATS; zs_episode.hpp)

@@ -29,10 +29,8 @@
 // workgroups of a mask launch over n envs
 static inline unsigned zs_mask_grid(int n) { return (unsigned)((n + ZS_MASK_ENVS - 1) / ZS_MASK_ENVS); }
 
-// the kernel is defined by the unit that sets ZS_DEFINE_MASK_KERNEL (k_mask.hip); others take the launch geometry
-#ifdef ZS_DEFINE_MASK_KERNEL
 // the predicate bits of slot s against agent a: 0..3 the slot stands on destination k, 4 zombie in range,
-// 5 other player present, 6 other player in healing range
+// 5 other player present, 6 other player in healing range (k_entity_act folds the same bits: zs_entity_act.hpp)
 __device__ __forceinline__ uint32_t mask_slot_bits(int s, int32_t sp, bool here, int a, int32_t ap, int r2, int np) {
     if (!here || s == a) return 0u;
     const int dx = unpack_x(sp) - unpack_x(ap), dy = unpack_y(sp) - unpack_y(ap);
@@ -42,6 +40,9 @@ __device__ __forceinline__ uint32_t mask_slot_bits(int s, int32_t sp, bool here,
     if (s >= np) return f | (dd <= r2 ? 16u : 0u);
     return f | 32u | (dd <= ZS_MASK_HEAL_R2 ? 64u : 0u);
 }
+
+// the kernel is defined by the unit that sets ZS_DEFINE_MASK_KERNEL (k_mask.hip); others take the launch geometry
+#ifdef ZS_DEFINE_MASK_KERNEL
 
 __global__ __launch_bounds__(ZS_MASK_BLOCK) void k_action_mask(Dev d, const uint8_t* __restrict__ env_mask,
                                                                uint64_t* __restrict__ out) {

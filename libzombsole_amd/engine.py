@@ -173,6 +173,9 @@ class Engine(object):
         self.masks = None  # the bound action-mask tensor (bind_action_masks), uint8 [N, A, 8]
         self.entities = None  # the bound entity-observation tensor (bind_entity_obs), int16 [N, A, ROW]
         self.entity_k = None  # its (kz, kp)
+        self.entity_act_ids = None  # the bound entity-action ids (bind_entity_act), int32 [N, A]
+        self.entity_act_masks = None  # the bound entity-action masks, uint8 [N, A, row_bytes]
+        self.entity_act_k = None  # their (kz, kp)
         self.nav = None  # the bound path-distance rows (nav_bind), int16 [N, A, F, 8]
         self.nav_args = None  # its (fields mask, max_dist)
         self.pilot = None  # the bound scripted triples (bind_autopilot), int32 [N, A, 3]; self.actions when bound into it
@@ -347,6 +350,90 @@ class Engine(object):
         self.entities = buf
         self.entity_k = (int(kz), int(kp)) if buf is not None else None
         return buf
+
+    # -- entity-targeted actions (zs_entity_act*): a table of 15 + kz + kp ids per agent over the entity observation's
+    # rows (libzombsole_amd/entity_act.py): ids int32 [N, A], masks uint8 [N, A, row_bytes], triples int32 [N, A, 3] ---
+    def _entity_act_k(self, kz, kp):
+        if kz is None and kp is None and self.entity_act_k is not None:
+            return self.entity_act_k
+        return self._entity_k(kz, kp)
+
+    def entity_act_layout(self, kz=None, kp=None):
+        """zs_entity_act_table as a dict: "nid", "row_bytes" (nid rounded up to 8) and the first id of the blocks
+        "attack_dir", "heal_dir", "zombie_rows", "player_rows", "end", with "kz" and "kp" (default: the bound ones, else
+        the bound entity observation's)."""
+        kz, kp = self._entity_act_k(kz, kp)
+        if ("zs_entity_act_table", kz, kp) not in self._layouts:
+            out = (C.c_int32 * len(_abi.ENTITY_ACT_TABLE_KEYS))()
+            self._call("zs_entity_act_table", kz, kp, out)
+            self._layouts[("zs_entity_act_table", kz, kp)] = {k: int(v) for k, v in zip(_abi.ENTITY_ACT_TABLE_KEYS, out) if k}
+        return dict(self._layouts[("zs_entity_act_table", kz, kp)], kz=kz, kp=kp)
+
+    def entity_act_decode(self, ids, mask=None, out=None, kz=None, kp=None):
+        """The triples of `ids` (int32 [N, A] on the device) on the current state, int32 [N, A, 3] (zs_entity_act_decode).
+        Envs where the uint8 device tensor `mask` is zero keep their rows.  Into `out` when given, else a new tensor."""
+        t = self.torch
+        kz, kp = self._entity_act_k(kz, kp)
+        self.entity_act_layout(kz, kp)  # ValueError on bad K values
+        check_tensor(ids, "entity_act_decode: ids", t.int32, self.device, self.N, (self.A,))
+        o = out if out is not None else t.zeros((self.N, self.A, 3), dtype=t.int32, device=self.device)
+        check_tensor(o, "entity_act_decode: out", t.int32, self.device, self.N, (self.A, 3))
+        self._call("zs_entity_act_decode", _ptr(mask), kz, kp, _ptr(ids), _ptr(o), self._stream())
+        return o
+
+    def entity_act_mask(self, mask=None, out=None, kz=None, kp=None):
+        """The table's masks of the current state, uint8 [N, A, row_bytes] (zs_entity_act_mask); bytes past nid are 0.
+        Envs where the uint8 device tensor `mask` is zero keep their bytes.  Into `out` when given, else into the bound
+        tensor (same kz, kp), else into a tensor this call allocates (zeroed)."""
+        t = self.torch
+        kz, kp = self._entity_act_k(kz, kp)
+        rb = self.entity_act_layout(kz, kp)["row_bytes"]
+        o = out
+        if o is None and self.entity_act_masks is not None and (kz, kp) == self.entity_act_k:
+            o = self.entity_act_masks
+        if o is None:
+            o = t.zeros((self.N, self.A, rb), dtype=t.uint8, device=self.device)
+        check_tensor(o, "entity_act_mask: masks", t.uint8, self.device, self.N, (self.A, rb), align=8)
+        self._call("zs_entity_act_mask", _ptr(mask), kz, kp, _ptr(o), self._stream())
+        return o
+
+    def entity_act_encode(self, triples, mask=None, out=None, kz=None, kp=None):
+        """The smallest id whose decoded triple equals each row of `triples` (int32 [N, A, 3]) on the current state, else
+        -1; int32 [N, A] (zs_entity_act_encode).  Envs where `mask` is zero keep their values."""
+        t = self.torch
+        kz, kp = self._entity_act_k(kz, kp)
+        self.entity_act_layout(kz, kp)
+        check_tensor(triples, "entity_act_encode: triples", t.int32, self.device, self.N, (self.A, 3))
+        o = out if out is not None else t.full((self.N, self.A), -1, dtype=t.int32, device=self.device)
+        check_tensor(o, "entity_act_encode: out", t.int32, self.device, self.N, (self.A,))
+        self._call("zs_entity_act_encode", _ptr(mask), kz, kp, _ptr(triples), _ptr(o), self._stream())
+        return o
+
+    def bind_entity_act(self, ids=None, masks=None, kz=4, kp=1):
+        """Bind `ids` (True: a new int32 [N, A] tensor) so that every step(), step_graph() and step_graphed() begins
+        with their decode into the step's actions, and `masks` (True: a new uint8 [N, A, row_bytes] tensor) so that every
+        step launches the table's masks into it (zs_entity_act_bind).  None / False for both unbinds.  self.entity_act_ids,
+        self.entity_act_masks and self.entity_act_k hold the binding.  Returns (ids, masks)."""
+        t = self.torch
+        ids = None if ids is False else ids
+        masks = None if masks is False else masks
+        if ids is None and masks is None:
+            self._call("zs_entity_act_bind", None, None, 0, 0)
+            self.entity_act_ids = self.entity_act_masks = self.entity_act_k = None
+            return None, None
+        kz, kp = int(kz), int(kp)
+        rb = self.entity_act_layout(kz, kp)["row_bytes"]
+        if ids is True:
+            ids = t.zeros((self.N, self.A), dtype=t.int32, device=self.device)
+        if masks is True:
+            masks = t.zeros((self.N, self.A, rb), dtype=t.uint8, device=self.device)
+        if ids is not None:
+            check_tensor(ids, "bind_entity_act: ids", t.int32, self.device, self.N, (self.A,))
+        if masks is not None:
+            check_tensor(masks, "bind_entity_act: masks", t.uint8, self.device, self.N, (self.A, rb), align=8)
+        self._call("zs_entity_act_bind", _ptr(ids), _ptr(masks), kz, kp)
+        self.entity_act_ids, self.entity_act_masks, self.entity_act_k = ids, masks, (kz, kp)
+        return ids, masks
 
     # -- path-distance fields (zs_nav*): walking distance to the objectives and to the zombies, int16 [N, A, F, 8] rows
     # and uint16 [n, H, W] frames (libzombsole_amd/nav.py) ---------------------------------------------------------

@@ -110,6 +110,20 @@ class MultiagentZombsoleEnv(object):
         rows = self._core.scripted_triples(policy)
         return {aid: to_action_dict(rows[i]) for i, aid in enumerate(self._ids)}
 
+    def entity_action_masks(self, kz=4, kp=1):
+        """Not in the reference: uint8 [num_agents, 15 + kz + kp] in possible_agents order, the entity action table's
+        masks on the current world; an agent that is not in the world has all zeros (libzombsole_amd/entity_act.py;
+        include/zombsole_mi355x.h, zs_entity_act_mask)."""
+        return self._core.entity_action_masks(kz, kp)
+
+    def entity_action(self, agent_id, id, kz=4, kp=1):
+        """Not in the reference: the action dict {"action_type": ..., "parameter": [dx, dy]} of entity-action `id` for
+        `agent_id` on the current world (zs_entity_act_decode); step() takes it."""
+        from ..autopilot import to_action_dict
+        ids = [0] * len(self._ids)
+        ids[self._ids.index(agent_id)] = int(id)
+        return to_action_dict(self._core.entity_action_triples(ids, kz, kp)[self._ids.index(agent_id)])
+
     def path_distances(self, fields=("objective", "zombies"), max_dist=None):
         """Not in the reference: int16 [A, F, 8], every possible agent's path-distance rows on the current world, in the
         order of the agent ids (libzombsole_amd/nav.py; include/zombsole_mi355x.h, zs_nav_obs)."""
@@ -196,6 +210,12 @@ class MultiAgentWrapper(object):
 
     def scripted_actions(self, policy="terminator"):
         return self.env.scripted_actions(policy)
+
+    def entity_action_masks(self, kz=4, kp=1):
+        return self.env.entity_action_masks(kz, kp)
+
+    def entity_action(self, agent_id, id, kz=4, kp=1):
+        return self.env.entity_action(agent_id, id, kz, kp)
 
     def path_distances(self, fields=("objective", "zombies"), max_dist=None):
         return self.env.path_distances(fields, max_dist)

@@ -88,6 +88,17 @@ class ZombsoleGymEnv(Env):
         from .autopilot import to_action_dict
         return to_action_dict(self._core.scripted_triples(policy)[0])
 
+    def entity_action_masks(self, kz=4, kp=1):
+        """Not in the reference: uint8 [15 + kz + kp], the agent's row of the entity action table's masks on the current
+        world (libzombsole_amd/entity_act.py; include/zombsole_mi355x.h, zs_entity_act_mask)."""
+        return self._core.entity_action_masks(kz, kp)[0]
+
+    def entity_action(self, agent_id, id, kz=4, kp=1):
+        """Not in the reference: the action dict {"action_type": ..., "parameter": [dx, dy]} of entity-action `id` for
+        the agent on the current world (zs_entity_act_decode); step() takes it."""
+        from .autopilot import to_action_dict
+        return to_action_dict(self._core.entity_action_triples([int(id)], kz, kp)[0])
+
     def path_distances(self, fields=("objective", "zombies"), max_dist=None):
         """Not in the reference: int16 [F, 8], the agent's path-distance rows on the current world
         (libzombsole_amd/nav.py; include/zombsole_mi355x.h, zs_nav_obs)."""

@@ -68,7 +68,10 @@ class BatchedZombsole(object):
                  observation_surroundings_width=21, observation_position_encoding_style="channels",
                  agent_weapons="rifle", obs_dtype=None, autoreset=True, device=None, lanes_per_env=0,
                  action_masks=False, env_params=False, episode_stats=False, render=False, entity_obs=None,
-                 grid_obs=True, autopilot=None, autopilot_into_actions=False, nav=None, nav_max_dist=32766):
+                 grid_obs=True, autopilot=None, autopilot_into_actions=False, nav=None, nav_max_dist=32766,
+                 entity_actions=False):
+        if entity_actions and entity_obs is None:
+            raise ValueError("entity_actions=True needs entity_obs=(kz, kp): the table's rows are the entity observation's")
         if surface == "single":
             b = _abi.single_env_config(num_envs, rules_name, player_names, map_name, agent_id, initial_zombies,
                                        minimum_zombies, observation_scope, observation_position_encoding,
@@ -102,6 +105,13 @@ class BatchedZombsole(object):
         # grid_obs=False: no grid observation is allocated or written; the entity tensor is the observation
         if entity_obs is not None:
             self.engine.bind_entity_obs(True, int(entity_obs[0]), int(entity_obs[1]))
+        # entity_actions=True: the entity action table over those rows (libzombsole_amd/entity_act.py): its masks bound
+        # and refreshed the same way, and an id buffer that step(ids) binds, so the step's first launch decodes it
+        self._eact_ids = None
+        if entity_actions:
+            kz, kp = int(entity_obs[0]), int(entity_obs[1])
+            self._eact_ids = self.torch.zeros((self.num_envs, self.engine.A), dtype=self.torch.int32, device=self.engine.device)
+            self.engine.bind_entity_act(None, True, kz, kp)
         # nav=("objective", "zombies") | "objective" | "zombies": path-distance rows (libzombsole_amd/nav.py) bound the
         # same way, refreshed at the same places
         if nav is not None:
@@ -143,6 +153,8 @@ class BatchedZombsole(object):
             eng.action_mask(mask)
         if eng.entities is not None:
             eng.entity_obs(mask)
+        if eng.entity_act_masks is not None:
+            eng.entity_act_mask(mask)
         if eng.nav is not None:
             eng.nav_obs(mask)
         if eng.pilot is not None:
@@ -166,6 +178,40 @@ class BatchedZombsole(object):
         the world self.obs shows.  Valid after every reset, step, restore / clone and load_checkpoint.  None without
         entity_obs=(kz, kp)."""
         return self.engine.entities
+
+    # -- entity-targeted actions (entity_actions=True): a table of 15 + kz + kp ids per agent -------------------------
+    @property
+    def n_entity_actions(self):
+        """NID = 15 + kz + kp, the ids of the entity action table (libzombsole_amd/entity_act.py).  None without
+        entity_actions=True."""
+        return None if self._eact_ids is None else self.engine.entity_act_layout()["nid"]
+
+    @property
+    def entity_action_masks(self):
+        """uint8 [N, A, NID] (a view of the engine's bound [N, A, row_bytes] tensor): entry i of agent a is 1 when the
+        reference would carry out the table's action i for it on the world self.obs shows; all 0 for an agent not in the
+        world.  Valid after every reset, step, restore / clone and load_checkpoint.  None without entity_actions=True."""
+        m = self.engine.entity_act_masks
+        return None if m is None else m[:, :, :self.n_entity_actions]
+
+    def encode_actions(self, triples=None):
+        """The table's ids of `triples` (int32 [N, A, 3]; default self.scripted_actions, the bound autopilot's: the
+        teacher's labels over this table) on the current world, int32 [N, A], -1 where the table has no such entry."""
+        if self._eact_ids is None:
+            raise ValueError("encode_actions: no entity action table (BatchedZombsole(entity_actions=True))")
+        if triples is None:
+            triples = self.scripted_actions
+            if triples is None:
+                raise ValueError("encode_actions: no triples given and no autopilot is bound")
+        t = self.torch
+        return self.engine.entity_act_encode(triples.to(self.engine.device).to(t.int32).contiguous())
+
+    def _bind_entity_ids(self, on):
+        """The id buffer bound (the step begins with its decode) or not (the step takes the caller's triples); the
+        masks stay bound.  A change of form drops the cached step graphs once."""
+        eng = self.engine
+        if (eng.entity_act_ids is not None) != on:
+            eng.bind_entity_act(self._eact_ids if on else None, eng.entity_act_masks, *eng.entity_act_k)
 
     def _observation(self):
         return self.engine.obs if self.engine.grid_obs else self.engine.entities
@@ -257,8 +303,16 @@ class BatchedZombsole(object):
         [N, A]), as MultiagentZombsoleEnv.step / ZombsoleGymEnv.step do per env
         (gym/multiagent_env.py:111-171, gym_env.py:99-145).  graph=True replays the step as one hipGraph
         launch reading the engine's action buffer (Engine.step_graphed); graph=False dispatches its
-        kernels one by one (zs_step)."""
+        kernels one by one (zs_step).  With entity_actions=True an integer [N, A] tensor holds ids of the entity
+        action table (0..6 are the Discrete(7) ids), written into the bound id buffer and decoded by the step's first
+        launch against each env's current world; an [N, A, 3] tensor is still taken as triples."""
         t = self.torch
+        if self._eact_ids is not None:
+            self._bind_entity_ids(actions.dim() == 2)
+            if actions.dim() == 2:  # the table's ids: the step's first launch decodes them into the action buffer
+                self._eact_ids.copy_(actions)
+                eng = self.engine
+                return self._stepped(eng.step_graphed(eng.actions) if graph else eng.step(eng.actions))
         if actions.dim() == 2:
             actions = self.discrete_to_triples(actions)
         if not graph:
