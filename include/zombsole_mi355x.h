@@ -753,7 +753,10 @@ int zs_profile_read(zs_handle* h, double out[8]);
  * "entity_act_kernel" the entity action table's kernels (zs_entity_act_*), "entity_act_ids_bound" and
  * "entity_act_mask_bound" whether ids and a mask buffer are bound (zs_entity_act_bind);
  * "step_tail_launch" the launch that carried the tail of the last zs_step queued or captured: the observation kernel,
- * or "k_tail" when the step launch wrote the observations itself or obs_dev was NULL ("" before any step).
+ * or "k_tail" when the step launch wrote the observations itself or obs_dev was NULL ("" before any step);
+ * "step_policy" where the last captured zs_step_graph step with a policy takes its actions from: "ahead" (the
+ * previous step's observation kernel left them, the tick copies them out: no policy launch), "k_gen_actions_ctr"
+ * (a launch of its own) or "step launch" (generated inside it); "" before any such capture.
  * Returns ZS_OK. */
 int zs_describe(zs_handle* h, char* buf, int32_t len);
 /* Diagnostics: out[0], out[1] = the two pending-reset list counts, out[2] = the deferred-respawn

@@ -94,8 +94,13 @@ struct zs_handle {
     GraphSet gsets[kGraphSets];
     uint64_t gclock = 0;
     bool graphs_stale = false;  // zs_entity_act_bind changed what a step launches: the sets are dropped before the next replay
-    uint64_t* d_gstep = nullptr;  // [0] policy step counter (the step's policy reads it, the step's tail advances it)
+    // the policy step counter's block (GS_*, zs_device.hpp: the step's policy reads the counter, the step's tail advances
+    // it) and the policy's triples kept one step ahead, int32 [N][A][3]: the handle's own, since a caller may write
+    // into its action buffer between replays
+    uint64_t* d_gstep = nullptr;
+    int32_t* d_ahead = nullptr;
     int graph_pol = 0;            // zs_step_graph is capturing a step with this policy (n_discrete), else 0
+    const char* step_policy = "";  // where the last captured policy step takes its actions from (zs_describe)
     // next-step reset work on a side stream, concurrent with the tick (the two touch disjoint envs);
     // the caller's stream joins it before the observations (step.side_stream, and the stream exists)
     int reset_side = 0;
@@ -708,6 +713,8 @@ static int seed_envs(zs_handle* h, int32_t env0, int32_t n, const uint64_t* seed
     ENTER(h, stream, s);
     HIPCHK(hipMemcpyAsync(h->d_seedbuf, seeds_host, sizeof(uint64_t) * n, hipMemcpyHostToDevice, s));
     HIPCHK(launch_seed(s, h->d, env0, n, h->d_seedbuf));
+    // the policy rows kept ahead were generated from the old seeds: no stamp, so the next policy step generates its own
+    if (h->d_gstep) HIPCHK(hipMemsetAsync(h->d_gstep + GS_STAMP, 0, 2 * sizeof(uint64_t), s));
     HIPCHK(hipStreamSynchronize(s));  // seeds_host may be freed by the caller on return
     return ZS_OK;
 }
@@ -822,7 +829,7 @@ extern "C" int zs_step(zs_handle* h, const int32_t* actions_dev, void* obs_dev, 
     // 1) rebuild the envs that ended at the previous call (list[p]); fused into the tick launch
     //    when the LDS images allow, else a k_reset launch first
     int q = 1 - h->rpar, rc = ZS_OK;
-    bool side = false;
+    bool side = false, ahead = false;
     if (!h->step.fused) {
         side = h->reset_side != 0;
         hipStream_t rs = s;
@@ -835,17 +842,29 @@ extern "C" int zs_step(zs_handle* h, const int32_t* actions_dev, void* obs_dev, 
         // stream right after the fork and ahead of the reset launch (captured in that order, the graph
         // starts the policy first: C3 173 M env-steps/s, against 167 with the reset launch captured first
         // and 169 with the policy inside the step launch); otherwise inside the step launch (no launch,
-        // no gap: 8 192 envs 110 -> 117 M env-steps/s)
-        if (h->graph_pol && side)
+        // no gap: 8 192 envs 110 -> 117 M env-steps/s).
+        // Where the step ends in an encoder / writer observation kernel (k_obs_ring, k_obs_pbring), that launch
+        // generated this step's triples a step early into the handle's rows, under its store stream, and leaves the
+        // next step's (Dev::pol_ahead): no policy launch, the tick copies the rows out (or generates them itself
+        // when the stamp does not name this step: the first replay, after zs_seed, another n_discrete)
+        ahead = h->graph_pol && side && obs_dev && !h->d.fobs &&
+                (h->obs.full.kind == OBSK_RING || h->obs.full.kind == OBSK_BRING);
+        if (h->graph_pol && side && !ahead)
             HIPCHK(launch_gen_actions_ctr(s, h->d, (const uint64_t*)h->d_gstep, h->graph_pol, (int32_t*)actions_dev));
-        TRY(launch_reset(h, h->d, 1, nullptr, h->d.fobs ? obs_dev : nullptr, rs));
-        if (side) HIPCHK(hipEventRecord(h->ev_rjoin, h->s_reset));
+        // ... and then the tick is captured ahead of the reset launch (below): the graph starts its nodes in the
+        // order of capture, several us apart, and the tick is the longer of the two
+        if (!ahead) {
+            TRY(launch_reset(h, h->d, 1, nullptr, h->d.fobs ? obs_dev : nullptr, rs));
+            if (side) HIPCHK(hipEventRecord(h->ev_rjoin, h->s_reset));
+        }
     }
     // this step's Dev: the handle's (whose pol_* and tail_* stay null) with the policy the step launch generates
     // itself, then (below) with the tail the step's last launch carries
     Dev d = h->d;
-    d.pol_n = side ? 0 : h->graph_pol;
-    d.pol_step = side ? nullptr : h->d_gstep;
+    d.pol_n = side && !ahead ? 0 : h->graph_pol;
+    d.pol_step = side && !ahead ? nullptr : h->d_gstep;
+    d.pol_ahead = ahead ? h->d_ahead : nullptr;
+    if (h->graph_pol) h->step_policy = ahead ? "ahead" : side ? "k_gen_actions_ctr" : "step launch";
     // 2) tick every other env; envs that end now are queued on list[q] for the next call.
     // Work-list counters: between calls the list the next step appends to (list[1 - rpar]) and the
     // deferred-respawn list are empty.  This step appends to list[q] and resp_list, drains list[p] and
@@ -858,6 +877,10 @@ extern "C" int zs_step(zs_handle* h, const int32_t* actions_dev, void* obs_dev, 
     const int p = h->rpar;
     TRY(launch_tick(h, d, actions_dev, rewards_dev, done_dev, trunc_dev, listed_dev, reset_dev, h->d_rlist[q],
                     h->d_rcount + q, obs_dev, s));
+    if (ahead) {  // the side stream's reset work, forked above (it drains list[p]: before the parity flips)
+        TRY(launch_reset(h, h->d, 1, nullptr, nullptr, h->s_reset));
+        HIPCHK(hipEventRecord(h->ev_rjoin, h->s_reset));
+    }
     h->rpar = q;
     // a launch failing after the tick was queued: the step's tail (the counter protocol above) is done
     // here instead, so the next step does not append after stale counts (not while capturing: a failed
@@ -1220,12 +1243,13 @@ extern "C" int zs_step_graph_n(zs_handle* h, uint64_t step0, int32_t n_discrete,
             if (gs.used < set->used) set = &gs;
         HIPCHK(destroy_graphs(*set));
         if (!h->d_gstep) {
-            TRY(dalloc(h, &h->d_gstep, 2));
+            TRY(dalloc(h, &h->d_gstep, GS_WORDS));
+            TRY(dalloc(h, &h->d_ahead, (size_t)h->d.N * h->d.A * 3));
         }
         // the policy step counter is the policy graphs' alone: a set without a policy (n_discrete = 0) neither reads
-        // nor advances it, so capturing one in mid-run leaves it where the policy graphs continue from
-        uint64_t init[2] = {step0, 0};
-        if (n_discrete > 0) HIPCHK(hipMemcpyAsync(h->d_gstep, init, sizeof(init), hipMemcpyHostToDevice, s));
+        // nor advances it, so capturing one in mid-run leaves it where the policy graphs continue from.  The stamp of
+        // the rows kept ahead stays: it names the step and n_discrete they were generated for, whatever step0 is
+        if (n_discrete > 0) HIPCHK(hipMemcpyAsync(h->d_gstep + GS_STEP, &step0, sizeof(step0), hipMemcpyHostToDevice, s));
         HIPCHK(hipStreamSynchronize(s));
         hipStream_t cs;
         HIPCHK(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
@@ -1622,7 +1646,8 @@ extern "C" int zs_describe(zs_handle* h, char* buf, int32_t len) {
              "\"entity_kp\": %d, \"autopilot_kernel\": \"k_autopilot\", \"autopilot_grid\": %u, \"autopilot_block\": %d, "
              "\"autopilot_bound\": %d, \"nav_bound\": %d, \"nav_fields\": %d, \"nav_max_dist\": %d, \"nav_kernel\": \"k_nav\", "
              "\"nav_envs_per_wg\": %d, \"nav_block\": %d, \"nav_lds_bytes\": %d, \"entity_act_kernel\": \"k_entity_act\", "
-             "\"entity_act_ids_bound\": %d, \"entity_act_mask_bound\": %d, \"step_tail_launch\": \"%s\"}",
+             "\"entity_act_ids_bound\": %d, \"entity_act_mask_bound\": %d, \"step_tail_launch\": \"%s\", "
+             "\"step_policy\": \"%s\"}",
              d.N, d.E, p.G, p.fused ? "k_step" : "k_tick", p.lds, p.resident, p.rw_cap,
              d.fobs ? "step launch" : obs_kernel_name(kf.kind), h->reset_side,
              p.reset_lds, p.defer_respawn ? "k_respawn" : "tick", p.tick_waves, p.rw_step,
@@ -1631,7 +1656,7 @@ extern "C" int zs_describe(zs_handle* h, char* buf, int32_t len) {
              h->rn.body_col ? h->rn.plan.bands : 0, h->rn.body_col ? ZS_RENDER_BLOCK : 0,
              h->ent_bound ? 1 : 0, h->ent_kz, h->ent_kp, zs_pilot_grid(d.N), ZS_PILOT_BLOCK, h->pilot_out ? 1 : 0,
              h->nav_bound ? 1 : 0, h->nav_fields, h->nav_max_dist, h->nav.envs_per_wg, h->nav.block, h->nav.lds_bytes,
-             h->eact_ids ? 1 : 0, h->eact_mask ? 1 : 0, h->step_last);
+             h->eact_ids ? 1 : 0, h->eact_mask ? 1 : 0, h->step_last, h->step_policy);
     return ZS_OK;
 }
 

@@ -124,6 +124,10 @@ struct Dev {
     // *pol_step with pol_n discrete actions (0: actions read from the caller's buffer)
     const uint64_t* pol_step;
     int pol_n;
+    // ... kept one step ahead (policy_ahead below): the handle's own triples [N][A][3], written by the step's
+    // observation kernel for the next step and read by that step's tick when the stamp beside the counter says
+    // they are the ones it would generate; null = the step launch generates them itself
+    int32_t* pol_ahead;
     // the step's tail (zs_step), done by the last launch of the step (the observation kernel, or
     // k_tail): zero the pending-list counter this step drained and the deferred-respawn counter (the
     // next step appends to them), advance the policy step counter; null fields = nothing to do
@@ -213,11 +217,26 @@ __device__ __forceinline__ int32_t hp_store_value(const Dev& d, int64_t v) {
     return (int32_t)v;
 }
 
+// The policy step counter's block (zs_step_graph; Dev::pol_step and Dev::tail_step point at word 0), uint64 each:
+//   GS_STEP   the step number the next policy step takes (the step's tail advances it)
+//   GS_NEXT   GS_STEP + 1, stored by the tick of a step that keeps the policy ahead: the word the observation kernel's
+//             producers read, since that launch's own tail advances GS_STEP while they run
+//   GS_STAMP  what Dev::pol_ahead holds: the step number, then n_discrete (0: nothing valid).  Written by the tail
+//             of the launch that produced the rows; cleared, in stream order, by zs_seed
+enum { GS_STEP = 0, GS_NEXT, GS_STAMP, GS_STAMP_N, GS_WORDS };
+
 // the step's tail (see Dev::tail_*), by one thread of the last launch of a zs_step
 __device__ __forceinline__ void step_tail(const Dev& d) {
     if (d.tail_cnt0) *d.tail_cnt0 = 0;
     if (d.tail_cnt1) *d.tail_cnt1 = 0;
-    if (d.tail_step) *d.tail_step += 1;
+    if (d.tail_step) {
+        const uint64_t t = d.tail_step[GS_STEP] + 1;
+        d.tail_step[GS_STEP] = t;
+        if (d.pol_ahead) {  // this launch's producers write step t's rows (policy_ahead)
+            d.tail_step[GS_STAMP] = t;
+            d.tail_step[GS_STAMP_N] = (uint64_t)d.pol_n;
+        }
+    }
 }
 
 // bench / parity action stream (libzombsole_amd/actions.py): agent a of env e at step t takes
@@ -241,6 +260,23 @@ __device__ __forceinline__ int policy_id(uint64_t seed, uint64_t step, int n, in
 __device__ __forceinline__ int32_t policy_action(uint64_t seed, uint64_t step, int n, int k) {
     const int a = k / 3;
     return c_discrete[policy_id(seed, step, n, a)][k - 3 * a];
+}
+
+// The producer, `nthr` threads (this one: tid) of a workgroup of the step's last launch: the triples of step GS_NEXT for
+// the workgroup's `count` envs item_env(0 .. count) into Dev::pol_ahead.  Every env of the launch belongs to one
+// workgroup, so the launch leaves the rows of all of them
+template <typename F>
+__device__ __forceinline__ void policy_ahead(const Dev& d, int count, int tid, int nthr, F item_env) {
+    const uint64_t step = d.pol_step[GS_NEXT];
+    const int A = d.A, n = d.pol_n;
+    for (int i = tid; i < count * A; i += nthr) {
+        const int t = i / A, a = i - t * A, e = item_env(t);
+        const int id = policy_id(d.seeds[e], step, n, a);
+        int32_t* o = d.pol_ahead + ((size_t)e * A + a) * 3;
+        o[0] = c_discrete[id][0];
+        o[1] = c_discrete[id][1];
+        o[2] = c_discrete[id][2];
+    }
 }
 
 __device__ __forceinline__ int32_t pack_xy(int x, int y) { return (int32_t)((uint32_t)(x & 0xffff) | ((uint32_t)y << 16)); }

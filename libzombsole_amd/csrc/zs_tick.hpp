@@ -1560,13 +1560,19 @@ __device__ __forceinline__ void tick_wg(const Dev& d0, int wg, const int32_t* ac
     };
     const int nmisc = MISC_N + 2 * A;
     int pmin = 0, pmax = 0;  // the leader's word (second load round)
+    // zs_step_graph's policy kept one step ahead (Dev::pol_ahead): the previous step's observation kernel left this
+    // step's triples when the stamp says so (one test, uniform over the launch); they are then read like a caller's,
+    // from the handle's rows, else generated here as without them.  The stamp, the rows and the generator's inputs
+    // are all loaded in this round, and the test made after it: no load waits for the stamp
+    const int32_t* asrc = dp->pol_ahead ? dp->pol_ahead : actions;
+    uint64_t stamp = 0, stamp_n = 0;
+    if (dp->pol_n) {
+        pstep = dp->pol_step[GS_STEP];
+        if (dp->pol_ahead) stamp = dp->pol_step[GS_STAMP], stamp_n = dp->pol_step[GS_STAMP_N];
+    }
     if (active) {
-        if (dp->pol_n) {
-            pseed = dp->seeds[e];
-            pstep = *dp->pol_step;
-        } else if (A) {
-            av = actions[(size_t)e * A * 3 + min(j, 3 * A - 1)];
-        }
+        if (dp->pol_n) pseed = dp->seeds[e];
+        if (A && (!dp->pol_n || dp->pol_ahead)) av = asrc[(size_t)e * A * 3 + min(j, 3 * A - 1)];
         needs_reset = dp->scal[S_NEEDRESET * N + e];
         n_order = dp->scal[S_NORDER * N + e];
         st = dp->rngst[e];
@@ -1591,11 +1597,12 @@ __device__ __forceinline__ void tick_wg(const Dev& d0, int wg, const int32_t* ac
     for (int u = 0; u < 8; u++)
         if (64 * u < dp->DW) bmv[u] = dp->obstbits[min(lane + 64 * u, dp->DW - 1)];
     stepping = active && needs_reset == 0;
+    const bool ahead = dp->pol_ahead && __builtin_amdgcn_readfirstlane(stamp == pstep && stamp_n == (uint64_t)dp->pol_n);
     if (active && dp->pol_n) {
         // zs_step_graph: the policy's actions for this step (zs_gen_actions' stream), written out to the
         // caller's action buffer as the policy kernel would (envs reset by this call included)
         for (int k = j; k < 3 * A; k += G) {
-            const int32_t v = policy_action(pseed, pstep, dp->pol_n, k);
+            const int32_t v = ahead ? (k == j ? av : asrc[(size_t)e * A * 3 + k]) : policy_action(pseed, pstep, dp->pol_n, k);
             ((int32_t*)actions)[(size_t)e * A * 3 + k] = v;
             if (stepping) LACT(c, k) = v;
         }
@@ -1944,6 +1951,8 @@ __global__ void __launch_bounds__(64, W) k_tick(Dev d, const int32_t* actions, d
                                              uint8_t* trunc_out, uint8_t* listed_out, uint8_t* reset_out,
                                              int* reset_list, int* reset_count, void* obs_out, int env0, int env1) {
     extern __shared__ __align__(16) uint8_t smem[];
+    // the step number the observation kernel's producers generate for (GS_NEXT, zs_device.hpp); nothing in this launch reads it
+    if (d.pol_ahead && blockIdx.x == 0 && threadIdx.x == 0) const_cast<uint64_t*>(d.pol_step)[GS_NEXT] = d.pol_step[GS_STEP] + 1;
     tick_wg<G, EARLY>(d, xcd_remap(blockIdx.x, gridDim.x), actions, rew, done_out, trunc_out, listed_out, reset_out, reset_list,
                reset_count, obs_out, env0, env1, (lu8*)smem);
 }
